@@ -14,6 +14,11 @@ frame is fixed), slabs are all-gathered and the fused gradient buffer is all-red
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step`, the phase times and the
+roofline of the timed window).  --full adds everything else the bench measures beside it: the sustained window, the other --via path,
+the changing frame, the deferred / deterministic / sort-every-build steps, the instrumented statistics step, the unsharded comparison of
+an N > 1 run and the CPU oracle baseline.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -35,6 +40,22 @@ sys.path.insert(0, REPO)
 from lidar_rt_amd import scenes  # noqa: E402
 
 HBM_PEAK_BYTES_PER_S = 8.0e12        # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3e12 achievable
+DUMP_ROWS = 65536                    # --dump-outputs: per-Gaussian rows kept (S1M: ~16 MB of gradients instead of 250 MB; image whole)
+
+
+def dump_outputs(path, out, g, P):
+    """--dump-outputs: the image, the hit weights and every gradient of one step as <path>/<name>.npy (float32).  Arrays with P rows
+    (one per Gaussian) keep the same seeded sample of DUMP_ROWS rows, in ascending order, when P is larger."""
+    os.makedirs(path, exist_ok=True)
+    rows = None
+    if P > DUMP_ROWS:
+        rows = torch.as_tensor(np.sort(np.random.default_rng(0).choice(P, DUMP_ROWS, replace=False)), device=out.device)
+    arrays = {"out": out, **{("accum" if k == "accum" else "grad_" + k): v for k, v in g.items()}}
+    for name, x in arrays.items():
+        x = x.detach()
+        if rows is not None and x.dim() > 0 and x.shape[0] == P:
+            x = x.index_select(0, rows)
+        np.save(os.path.join(path, name + ".npy"), x.float().cpu().numpy())
 
 
 def algorithmic_bytes(C: float, K: float, deg: int = 3):
@@ -155,23 +176,23 @@ def main():
                     "training step -- consumes; nothing else has to be synchronised); dense = all_reduce of the flat buffer (replicated); owner = "
                     "every Gaussian's gradient is reduced to its owning rank only (reduce-scatter semantics: NOT a complete training exchange, "
                     "parameters and Adam moments of the touched rows would still have to be synchronised)")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="length of the SUSTAINED window that runs in front of the timed one (whole blocks of --steps until it "
+    ap.add_argument("--min-seconds", type=float, default=3.0, help="(--full) length of the SUSTAINED window that runs in front of the timed one (whole blocks of --steps until it "
                     "lasts at least this long; clocks and caches are warm afterwards, and driver-side telemetry sees the GPU busy).  It is reported as `sustained` "
                     "BESIDE `value`; `value` itself always comes from EXACTLY --steps steps, bracketed by barrier + synchronize.  0 = no sustained window")
-    ap.add_argument("--check-sum", action="store_true", help="add checksums of the (all-gathered / all-reduced) results")
+    ap.add_argument("--check-sum", action="store_true", help="add checksums of the last timed step's (all-gathered / all-reduced) results")
     ap.add_argument("--via", default="direct", choices=["direct", "tracer"], help="direct (default): the step drives the `_C` binding through ShardedTracer "
                     "with preallocated gradient views; tracer: the DROP-IN path a maintainer gets -- diff_lidar_tracer.Tracer -> torch.autograd -> `_C` "
                     "(fresh output / gradient tensors per call, the three dead zero outputs), N = 1 only.  The line always carries the other path's "
                     "rays/s as `drop_in_path` / `direct_path` when --both-paths is given")
     ap.add_argument("--both-paths", dest="both_paths", action="store_true", default=True,
-                    help="(default on one GPU) time the other --via path too, same window length, and report it beside `value` as `drop_in_path` / `direct_path`")
+                    help="(--full, default on one GPU) time the other --via path too, same window length, and report it beside `value` as `drop_in_path` / `direct_path`")
     ap.add_argument("--no-both-paths", dest="both_paths", action="store_false", help="time only the --via path")
     ap.add_argument("--no-vary", dest="vary", action="store_false", help="skip the `value_varying` window")
     ap.add_argument("--no-deferred", action="store_true", help="skip the `value_deferred_accum` window (the training configuration: hit weights written by the backward)")
-    ap.add_argument("--pose-inside", action="store_true", help="--vary poses 0.1 m from clutter instead of inside the scene's empty cylinder: hundreds of rays start closer than "
+    ap.add_argument("--pose-inside", action="store_true", help="(--full) --vary poses 0.1 m from clutter instead of inside the scene's empty cylinder: hundreds of rays start closer than "
                     "0.2 m to a quad and take the literal K-buffer replay (k_fwd_near); reported as `value_varying.near_rays_per_frame` / `near_us`")
     ap.add_argument("--print-launch", action="store_true", help="with --gpus N > 1 and no torch.distributed environment: print the launch command as JSON and exit (tests)")
-    ap.add_argument("--vary", action="store_true", default=True, help="(default on one GPU) a second timed window in which the frame CHANGES from step to step like in training "
+    ap.add_argument("--vary", action="store_true", default=True, help="(--full, default on one GPU) a second timed window in which the frame CHANGES from step to step like in training "
                     "(train.py:125-148 draws another frame per iteration and the optimizer moves the parameters): 4 sensor poses (yawed / translated ray sets) "
                     "in rotation and an Adam-sized perturbation of means / scales / opacities between steps.  Reported as `value_varying` BESIDE `value`: "
                     "it shows what the temporal speculation (per-tile learned slab widths, Morton box of the previous build, speculated hit counts) is worth "
@@ -185,7 +206,14 @@ def main():
                     "scripts use it so that every kernel of the trace is a kernel of a regular step (the counters' k_fwd_cr4<.., true> instantiation is not)")
     ap.add_argument("--refit-every", type=int, default=0, help="K > 0: K lrt_refit calls between full LBVH builds (NOT the headline "
                     "configuration: the reference rebuilds its acceleration structure on every call, and so does the default step)")
+    ap.add_argument("--full", action="store_true", help="also run every window and check beside the headline (sustained window, other --via path, "
+                    "changing frame, deferred / deterministic / sort-every-build steps, statistics step, N = 1 comparison, CPU baseline); their "
+                    "--no-* switches still apply.  Without it a run only warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (image, hit weights, gradients) "
+                    f"as DIR/<name>.npy, float32; per-Gaussian arrays of more than {DUMP_ROWS} rows as a fixed seeded sample of {DUMP_ROWS} rows")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))                      # re-enters this file once per rank under torch.distributed.run
@@ -289,7 +317,7 @@ def main():
     # the same count).  It is reported beside `value` and leaves clocks / caches / the library's speculation warm for the timed window.
     st.set_option("timing_every", max(1, args.time_every))
     reps, sustained = 0, None
-    if args.min_seconds > 0 and args.steps > 0:
+    if args.full and args.min_seconds > 0:
         barrier(); tc = time.perf_counter()
         for _ in range(args.steps):
             step()
@@ -318,7 +346,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps_run):
-        step()
+        last = step()
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -332,14 +360,32 @@ def main():
     if sustained is not None and any(kt[k_][1] == 0 for k_ in ("build", "fwd", "bwd")):
         kt = kts                                                      # a window shorter than --time-every steps holds no sample: the sustained window's averages
 
-    # ---- N > 1: every rank's own compute (its library regions: build + forward + backward), and the unsharded step of the same workload on rank 0
+    # ---- what the last timed step returned, before any other window overwrites the tracer's buffers
+    out, g = last
+    cks = None
+    if args.check_sum:
+        # owner exchange: a Gaussian's gradient is complete on its owner only -> sum over the owned rows, then over the ranks
+        def _abs_sum(x, rows=None):
+            x = x.double().abs().reshape(x.shape[0], -1)
+            return (x[rows] if rows is not None else x).sum()
+        own = (tr.last_owner == rank) if (world > 1 and tr.last_exchange == "owner") else None
+        vals = torch.stack([out.double().abs().sum(), _abs_sum(g["means"], own), _abs_sum(g["shs"], own),
+                            (g["accum"].double()[own] if own is not None else g["accum"].double()).sum()])
+        if own is not None:
+            part = vals[1:].clone(); dist.all_reduce(part, op=dist.ReduceOp.SUM); vals[1:] = part
+        cks = dict(zip(("out", "d_means", "d_shs", "accum"), [float(v) for v in vals.tolist()]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, g, int(sc["means"].shape[0]))
+    del out, g, last
+
+    # ---- N > 1: every rank's own compute (its library regions: build + forward + backward), and (--full) the unsharded step of the same workload on rank 0
     per_rank_ms, value_n1 = None, None
     if world > 1:
         mine = torch.tensor([kt[k_][0] / max(kt[k_][1], 1) for k_ in ("build", "fwd", "bwd")], dtype=torch.float64, device=dev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank_ms = [{"build": float(a_[0]), "forward": float(a_[1]), "backward": float(a_[2]), "sum": float(a_.sum())} for a_ in allr]
-        if rank == 0:
+        if rank == 0 and args.full:
             tr1 = ShardedTracer(exchange=args.exchange, world=1, rank=0)
             for kv in args.opt:
                 k_, v_ = kv.split("="); tr1.backend.state.set_option(k_, int(v_))
@@ -363,7 +409,7 @@ def main():
         barrier()
 
     other = None
-    if args.both_paths and world == 1:
+    if args.full and args.both_paths and world == 1:
         ostep = step_direct if args.via == "tracer" else step_tracer
         for _ in range(max(args.warmup, 1)):
             ostep()
@@ -376,7 +422,7 @@ def main():
     # the forward issues no float atomic per composited hit, the backward's Gaussian-ordered reduction writes the same sums (train.py reads
     # them after loss.backward() only: :156, :219).  NOT the headline: `value` keeps the reference's contract (weights complete at the forward)
     deferred = None
-    if world == 1 and not args.no_deferred:
+    if args.full and world == 1 and not args.no_deferred:
         tr_d = ShardedTracer(exchange=args.exchange, deferred_accum=True)
         for kv in args.opt:
             k_, v_ = kv.split("="); tr_d.backend.state.set_option(k_, int(v_))
@@ -411,7 +457,7 @@ def main():
     # ---------------- the bit-reproducible step (ShardedTracer(deterministic=True) / train --deterministic): gradient sums in a fixed order (a second pass over the
     # records in k_bk_sort, k_bwd_fixup), a forward without learnt tables that waits for its status words.  NOT the headline: what reproducibility costs.
     determ = None
-    if world == 1 and not args.no_deferred and not args.no_build_in_step and args.refit_every <= 0:
+    if args.full and world == 1 and not args.no_deferred and not args.no_build_in_step and args.refit_every <= 0:
         tr_t = ShardedTracer(exchange=args.exchange, deterministic=True)
         tr_t.backend.state.set_option("timing_every", max(1, args.time_every))
 
@@ -437,7 +483,7 @@ def main():
     # ---------------- the step with a full Morton sort in EVERY build (library option carry_order=0; the headline's builds keep the order of the last
     # sort for up to 32 builds -- what a training loop's builds do between optimizer steps -- and sort again when it has decayed)
     full_sort = None
-    if world == 1 and not args.no_deferred and not args.no_build_in_step and args.refit_every <= 0:
+    if args.full and world == 1 and not args.no_deferred and not args.no_build_in_step and args.refit_every <= 0:
         st.set_option("carry_order", 0)
         for _ in range(3):
             step()
@@ -455,7 +501,7 @@ def main():
 
     # ---------------- the same step on a frame that changes every iteration (--vary)
     varying = None
-    if args.vary and world == 1:
+    if args.full and args.vary and world == 1:
         n_pose = 4
         # the sensor stays inside the scene's empty cylinder (r < 2 m around the origin): a pose inside the clutter would make hundreds of
         # "near rays" (a quad closer than 0.2 m: the literal K-buffer replay of lrt_near.inc), which is a property of that pose, not of a moving frame
@@ -517,25 +563,14 @@ def main():
         step()                                                                         # back on the fixed frame for the statistics step below
 
     # ---------------- one instrumented step for the traversal statistics (untimed)
-    if not args.no_stats_step:
+    hs = {}
+    if args.full and not args.no_stats_step:
         st.enable_stats(True)
-    out, g = step()
-    torch.cuda.synchronize()
-    hs = st.get_stats(dev) if not args.no_stats_step else {}
-    st.enable_stats(False)
+        step()
+        torch.cuda.synchronize()
+        hs = st.get_stats(dev)
+        st.enable_stats(False)
 
-    cks = None
-    if args.check_sum:
-        # owner exchange: a Gaussian's gradient is complete on its owner only -> sum over the owned rows, then over the ranks
-        def _abs_sum(x, rows=None):
-            x = x.double().abs().reshape(x.shape[0], -1)
-            return (x[rows] if rows is not None else x).sum()
-        own = (tr.last_owner == rank) if (world > 1 and tr.last_exchange == "owner") else None
-        vals = torch.stack([out.double().abs().sum(), _abs_sum(g["means"], own), _abs_sum(g["shs"], own),
-                            (g["accum"].double()[own] if own is not None else g["accum"].double()).sum()])
-        if own is not None:
-            part = vals[1:].clone(); dist.all_reduce(part, op=dist.ReduceOp.SUM); vals[1:] = part
-        cks = dict(zip(("out", "d_means", "d_shs", "accum"), [float(v) for v in vals.tolist()]))
     if rank == 0:
         n_rays = H * W
         ms_per_step = 1e3 * elapsed / steps_run
@@ -551,7 +586,8 @@ def main():
         else:
             # the bucketed backward replays the hit record: nothing is counted twice (S1M: composited = 3,939,575 = 30.06 x 131,072 exactly)
             C = hs.get("candidates", 0) / max(rays_local, 1); K = hs.get("composited", 0) / max(rays_local, 1)
-            ck_src = "HIP counters of this run (forward traversal of the instrumented step)"
+            ck_src = ("HIP counters of this run (forward traversal of the instrumented step)" if hs else
+                      "not counted (C = K = 0): the instrumented step runs with --full only")
         bf, bb = algorithmic_bytes(C, K, deg)
         ms_f = kt["fwd"][0] / max(kt["fwd"][1], 1); ms_b = kt["bwd"][0] / max(kt["bwd"][1], 1)
         ms_build = kt["build"][0] / max(kt["build"][1], 1)
@@ -632,7 +668,7 @@ def main():
             "metric": "LiDAR rays/s fwd+bwd @1M Gaussians, 2048x64 sweep; % HBM roofline",
             "value": value, "unit": "rays/s", "n_gpus": world, "steps": steps_run, "steps_requested": args.steps, "warmup": args.warmup,
             "timed_window_s": elapsed,
-            # the same step over a window of --min-seconds, run in front of the timed one
+            # (--full) the same step over a window of --min-seconds, run in front of the timed one
             "sustained": sustained,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
@@ -666,7 +702,7 @@ def main():
             res["value_sort_every_build"] = full_sort
         if args.check_sum:
             res["checksums"] = cks
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(sc, ro, rd, deg, bg_np, dL_np)
             except Exception as ex:  # the oracle is test infrastructure; never fail the bench on it

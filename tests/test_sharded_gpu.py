@@ -37,7 +37,7 @@ def test_bench_starts_its_own_ranks():
     the line says two ranks ran and carries the N = 1 value of the same workload, every rank's compute and the exchange times."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MASTER_ADDR="127.0.0.1", LRT_SINGLE_DEVICE="1", LRT_DIST_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--workload", "s10k", "--no-cpu-baseline", "--min-seconds", "0"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--workload", "s10k", "--no-cpu-baseline", "--min-seconds", "0", "--full"]
     out = subprocess.run(cmd, check=True, env=env, cwd=REPO, timeout=600, capture_output=True, text=True).stdout
     b = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert b["n_gpus"] == 2 and b["steps"] == 4 and b["steps_requested"] == 4

@@ -4,5 +4,5 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for v in "$@"; do
   if [ "$v" = "-" ]; then unset LRT_HIP_LIB; else export LRT_HIP_LIB=$R/lidar_rt_amd/csrc/liblrt_ab_$v.so; fi
-  python $R/bench.py --no-cpu-baseline --no-both-paths --no-vary --min-seconds 1.5 --steps 100 --check-sum $AB_ARGS 2>/dev/null | python $R/tools/benchline.py "$v"
+  python $R/bench.py --full --no-cpu-baseline --no-both-paths --no-vary --min-seconds 1.5 --steps 100 --check-sum $AB_ARGS 2>/dev/null | python $R/tools/benchline.py "$v"
 done
