@@ -45,7 +45,7 @@ typedef struct lrt_state lrt_state;
 #define LRT_ERR_STATE (-3)
 
 /* ABI version of this header (bumped on any signature change); lrt_abi_version() is what the loaded library was built from. */
-#define LRT_ABI_VERSION 4
+#define LRT_ABI_VERSION 5
 int lrt_abi_version(void);
 /* 1: this is the cross-check library (compiled with -DLRT_LEGACY: liblrt_hip_legacy.so, tests only), which also carries the kernel
  * generations that lost their measurements -- bwd_mode 1 / 2, colours inside the trace kernel (defer_colour = 0), the level-by-level tree
@@ -135,6 +135,19 @@ int lrt_backward_accum(lrt_state* st, int H, int W, const float* ray_o, const fl
                        const float* opacities, const float* shs, const float* background, const float* out9,
                        const float* dL_dout9, float* d_means, float* d_shs, float* d_opacities, float* d_scales,
                        float* d_rotations, float* accum_out, void* stream);
+
+/* lrt_backward_accum that also returns the gradients w.r.t. the RAYS (ABI 5): d_ray_o = dL/dray_o and d_ray_d = dL/dray_d, (H, W, 3) each,
+ * every element written (rays without a composited hit get zero).  Per composited hit, with t = n.(mu - o) / n.d and x = o + t d:
+ * v = dL/dx - w n (w = dL/dt / n.d), dL/do += v, dL/dd += t v; the view-dependent colour adds its SH-basis term once per ray (through the
+ * normalisation of a non-unit d).  The same per-hit dL/dalpha as the Gaussian gradients, reference deviations D1 and D3 included; channels
+ * 4 (W) and 8 (T) carry no gradient.  Plain stores, no float atomics: bit-reproducible in every mode.  The Gaussian gradients, `accum_out`
+ * and the outputs are the same bits as without ray gradients; the bucketed replay (bwd_mode 3) costs one extra launch.  bwd_mode 1 and 2
+ * (cross-check library): LRT_ERR_STATE.  d_ray_o == d_ray_d == NULL: exactly lrt_backward_accum. */
+int lrt_backward_rays(lrt_state* st, int H, int W, const float* ray_o, const float* ray_d, int P, int M,
+                      int sh_degree, const float* means, const float* scales, const float* rotations,
+                      const float* opacities, const float* shs, const float* background, const float* out9,
+                      const float* dL_dout9, float* d_means, float* d_shs, float* d_opacities, float* d_scales,
+                      float* d_rotations, float* accum_out, float* d_ray_o, float* d_ray_d, void* stream);
 
 /* Serial number of the most recent lrt_forward on this state.  The composited-hit record that the replay backward
  * uses belongs to THAT forward: a caller that runs several forwards before a backward compares the serial it saved

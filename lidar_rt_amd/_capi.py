@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LRT_HIP_LIB") or os.path.join(HERE, "csrc", "liblrt_hip.so")   # env override: A/B builds
 
 EXPORTS = ("lrt_abi_version", "lrt_last_error", "lrt_create", "lrt_destroy", "lrt_build", "lrt_build_for_rays", "lrt_build_for_slab", "lrt_forward",
-           "lrt_refit", "lrt_backward", "lrt_backward_accum", "lrt_enable_stats", "lrt_get_stats", "lrt_set_option", "lrt_get_option", "lrt_debug_read", "lrt_enable_timing", "lrt_get_timing", "lrt_forward_serial", "lrt_built_count", "lrt_check_forward", "lrt_has_legacy",
+           "lrt_refit", "lrt_backward", "lrt_backward_accum", "lrt_backward_rays", "lrt_enable_stats", "lrt_get_stats", "lrt_set_option", "lrt_get_option", "lrt_debug_read", "lrt_enable_timing", "lrt_get_timing", "lrt_forward_serial", "lrt_built_count", "lrt_check_forward", "lrt_has_legacy",
            "lrt_status_to_device", "lrt_xchg_msg_words", "lrt_xchg_pack", "lrt_xchg_apply",
            # include/lrt_chamfer.h
            "lrt_chamfer_create", "lrt_chamfer_destroy", "lrt_chamfer_forward", "lrt_chamfer_backward",
@@ -23,7 +23,7 @@ EXPORTS = ("lrt_abi_version", "lrt_last_error", "lrt_create", "lrt_destroy", "lr
            # include/lrt_preprocess.h
            "lrt_preprocess_forward", "lrt_preprocess_backward")
 
-ABI_VERSION = 4          # LRT_ABI_VERSION of include/lrt.h this binding was written against
+ABI_VERSION = 5          # LRT_ABI_VERSION of include/lrt.h this binding was written against
 
 _lib = None
 
@@ -64,6 +64,9 @@ def load():
     lib.lrt_backward_accum.restype = ci
     lib.lrt_backward_accum.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp,
                                        vp, vp, vp, vp, vp, vp, vp]
+    lib.lrt_backward_rays.restype = ci
+    lib.lrt_backward_rays.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.lrt_enable_stats.restype = ci; lib.lrt_enable_stats.argtypes = [vp, ci]
     lib.lrt_get_stats.restype = ci; lib.lrt_get_stats.argtypes = [vp, C.POINTER(C.c_uint64), vp]
     lib.lrt_enable_timing.restype = ci; lib.lrt_enable_timing.argtypes = [vp, ci]

@@ -244,13 +244,19 @@ __global__ void __launch_bounds__(BUCKET ? 1024 : 64, BUCKET ? (FAST ? 8 : 4) : 
 // a ray composites 30 hits on average, so a wave per ray left half of the lanes idle and every wave walked 16 rays one memory round trip
 // after the other.  Lanes 0..31 take ray 2k, lanes 32..63 ray 2k + 1 of the group; the prefix product / sums run inside each half
 // (the wave scans without their last DPP step), a ray with more than 32 hits loops with carries taken from lane 31 / 63.
-__global__ void __launch_bounds__(1024, 8) k_bwd_prep2(const TraceParams p)
+//
+// MODE 1 (lrt_backward_rays, one extra launch behind MODE 0): the same replay of the same record with the same dL/dalpha per hit, but instead
+// of the hit's bucket record it forms the hit's share of the RAY's gradient (lrt_hit_ray_backward on the Gaussian's geometry, and the colour
+// term dL/dbasis from its SH row), sums it inside the half-wave that owns the ray and stores 6 floats per ray.  No cursors, no clearing, no
+// LDS; a register budget of its own (MODE 0 stays at its 64).
+template <int MODE>
+__global__ void __launch_bounds__(1024, MODE == 0 ? 8 : 1) k_bwd_prep2(const TraceParams p)
 {
     extern __shared__ unsigned s_cur[];
     const int lane = threadIdx.x & 63, hl = lane & 31, half = lane >> 5;
     const float bg0 = p.bg[0], bg1 = p.bg[1], bg2 = p.bg[2];
     if (bwd_guard_skips(p)) return;
-    if (p.zero_in_prep) {
+    if (MODE == 0 && p.zero_in_prep) {
         const size_t tid_ = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthr_ = (size_t)gridDim.x * blockDim.x, P_ = (size_t)p.P;
         // Round 6: the gradient tensors are cleared HERE, whole, by streaming 16-byte stores that this latency-bound kernel (its waves wait 70 % of
         // the time for the dependent loads of the replay) has the memory pipe free for -- instead of k_bk_sort storing a row of zeros per Gaussian
@@ -263,7 +269,7 @@ __global__ void __launch_bounds__(1024, 8) k_bwd_prep2(const TraceParams p)
         if (p.accum) bk_zero_span(p.accum, P_, tid_, nthr_);
         if (p.zero_in_prep != 2) bk_zero_span(p.d_shs, 3 * P_ * (size_t)p.M, tid_, nthr_);      // (an unaligned table: up front like the others)
     }
-    {
+    if (MODE == 0) {
         __shared__ unsigned s_h16[16];
         bk_setup_cursors(p, s_cur, s_h16);
     }
@@ -285,7 +291,7 @@ __global__ void __launch_bounds__(1024, 8) k_bwd_prep2(const TraceParams p)
         const float* dLp = p.dL_dout + LRT_NCH * rr; const float* fp = p.out9_in + LRT_NCH * rr;
         const float dL0 = dLp[0], dL1 = dLp[1], dL2 = dLp[2], dL3 = dLp[3], dL5 = dLp[5], dL6 = dLp[6], dL7 = dLp[7];
         const float f0 = fp[0], f1 = fp[1], f2 = fp[2], f3 = fp[3], f5 = fp[5], f6 = fp[6], f7 = fp[7], f8 = fp[8];
-        if (hl < 4 && n > 0) {
+        if (MODE == 0 && hl < 4 && n > 0) {
             float4 v;
             if (hl == 0) v = make_float4(p.ray_o[3 * rr], p.ray_o[3 * rr + 1], p.ray_o[3 * rr + 2], dL3);
             else if (hl == 1) v = make_float4(p.ray_d[3 * rr], p.ray_d[3 * rr + 1], p.ray_d[3 * rr + 2], 0.f);
@@ -297,6 +303,12 @@ __global__ void __launch_bounds__(1024, 8) k_bwd_prep2(const TraceParams p)
         const bool need_n = (dL5 != 0.f) || (dL6 != 0.f) || (dL7 != 0.f);
         const bool any_n = __any(need_n && n > 0);
         float T_run = 1.f, rC0 = 0.f, rC1 = 0.f, rC2 = 0.f, rD = 0.f, rN0 = 0.f, rN1 = 0.f, rN2 = 0.f;
+        float o[3], d[3], go[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f}, db[16];     // MODE 1: the ray, this lane's share of its gradient
+        if (MODE == 1) {
+            for (int i = 0; i < 3; i++) { o[i] = p.ray_o[3 * rr + i]; d[i] = p.ray_d[3 * rr + i]; }
+#pragma unroll
+            for (int k = 0; k < 16; k++) db[k] = 0.f;
+        }
         for (int cb = 0; __any(cb < n); cb += 32) {
             const int j = cb + hl;
             const bool live = j < n;
@@ -329,15 +341,34 @@ __global__ void __launch_bounds__(1024, 8) k_bwd_prep2(const TraceParams p)
             dLa += dL3 * (Tk * t - (f3 - sD) * i1a);
             if (need_n) dLa += dL5 * (Tk * n0 - (f5 - sN0) * i1a) + dL6 * (Tk * n1 - (f6 - sN1) * i1a) + dL7 * (Tk * n2 - (f7 - sN2) * i1a);   // D3
             dLa *= (ao > LRT_ALPHA_MAX) ? 0.f : 1.f;                 // backward.cu:607-608
-            if (live) {
+            if (MODE == 0 && live) {
                 const unsigned slot = atomicAdd(&s_cur[(unsigned)g >> p.bk_shift], 1u);
                 if (slot < p.rec_cap)
                     p.brec[slot] = make_uint4((r << p.bk_shift) | ((unsigned)g & gmask), __float_as_uint(t), __float_as_uint(dLa), __float_as_uint(cl0 ? -wgt : wgt));
+            }
+            if (MODE == 1 && live) {                                 // the hit's share of the ray gradient, as bwd_hit / k_bwd_reduce4 see the hit
+                const float mu[3] = {p.means[3 * (size_t)g], p.means[3 * (size_t)g + 1], p.means[3 * (size_t)g + 2]};
+                const float sc[2] = {p.scales[2 * (size_t)g], p.scales[2 * (size_t)g + 1]};
+                const float q[4] = {p.rots[4 * (size_t)g], p.rots[4 * (size_t)g + 1], p.rots[4 * (size_t)g + 2], p.rots[4 * (size_t)g + 3]};
+                LrtHitGeom hg;
+                lrt_hit_geom(o, d, t, mu, sc, q, p.mod, &hg);
+                lrt_hit_ray_backward(&hg, d, t, p.opac[g] * dLa, dL3 * wgt, go, gd);
+                const float r0 = cl0 ? 0.f : dL0 * wgt, r1 = dL1 * wgt, r2 = dL2 * wgt;
+                const float* sh = p.shs + (size_t)g * p.M * 3;
+#pragma unroll
+                for (int k = 0; k < 16; k++)
+                    if (k < p.nsh) db[k] += r0 * sh[3 * k] + r1 * sh[3 * k + 1] + r2 * sh[3 * k + 2];
             }
             // carries for rays with more than 32 composited hits
             T_run *= half_last(incl, half);
             rC0 = half_last(sC0, half); rC1 = half_last(sC1, half); rC2 = half_last(sC2, half); rD = half_last(sD, half);
             if (any_n) { rN0 = half_last(sN0, half); rN1 = half_last(sN1, half); rN2 = half_last(sN2, half); }
+        }
+        if (MODE == 1) {                                             // colour term once per lane, then the half-wave's sums; lane 31 / 63 stores
+            lrt_sh_basis_vjp(p.deg, d, db, gd);
+            float s6[6];
+            for (int i = 0; i < 3; i++) { s6[i] = half_sum_f(go[i]); s6[3 + i] = half_sum_f(gd[i]); }
+            if (hl == 31 && valid && n > 0) store_ray_grad(p, r, s6, s6 + 3);
         }
     }
 }

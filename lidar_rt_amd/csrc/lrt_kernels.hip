@@ -311,6 +311,9 @@ struct TraceParams {
     unsigned* bk_base;                     // [bk_nb + 1] first record of a bucket
     uint4* brec2; unsigned* bkg;          // the records in Gaussian order (ray, t, dL/dalpha, +-w) and their Gaussian
     int bk_shift, bk_nb, bk_ng, bk_rpg, bk_cw;   // (bk_cw: see bk_group_ray)
+    // backward, lrt_backward_rays: dL/dray_o and dL/dray_d, (H, W, 3) each, cleared before the backward; every ray with a composited hit is
+    // stored once, by its owner (k_bwd_prep2<1>, the re-trace k_trace<true> or the near-ray replay).  Null: no ray gradients
+    float* d_ray_o; float* d_ray_d;
 };
 
 
@@ -373,7 +376,7 @@ __device__ __forceinline__ float wave_incl_sum(float x)                  // incl
     return x;
 }
 
-struct RayAcc { float T, C0, C1, C2, Dd, Wt, N0, N1, N2; };
+struct RayAcc { float T, C0, C1, C2, Dd, Wt, N0, N1, N2; float go[3], gd[3]; };   // go / gd: the ray's gradient so far (p.d_ray_o only)
 
 // One slot per ACTIVE lane with a single atomic per wave (callable from divergent code).
 __device__ __forceinline__ unsigned wave_alloc(unsigned* counter)
@@ -470,8 +473,24 @@ __device__ __forceinline__ float bwd_hit(const TraceParams& p, const float* o, c
             unsafeAtomicAdd(dsh + 3 * k + 1, b[k] * r1);
             unsafeAtomicAdd(dsh + 3 * k + 2, b[k] * r2);
         }
+    if (p.d_ray_o) {                                         // ray gradients (lrt_backward_rays): this hit's share, no atomics (the ray is the caller's)
+        lrt_hit_ray_backward(&hg, d, t, dL_dG, dL[3] * wgt, a.go, a.gd);
+        if (nsh > 1) {
+            const float* sh = p.shs + (size_t)g * p.M * 3;
+            float db[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) db[k] = (k < nsh) ? r0 * sh[3 * k] + r1 * sh[3 * k + 1] + r2 * sh[3 * k + 2] : 0.f;
+            lrt_sh_basis_vjp(p.deg, d, db, a.gd);
+        }
+    }
     a.T = T * (1.f - alpha);
     return alpha;
+}
+
+// The ray gradient of ray r, stored whole by its one owner.
+__device__ __forceinline__ void store_ray_grad(const TraceParams& p, size_t r, const float* go, const float* gd)
+{
+    for (int i = 0; i < 3; i++) { p.d_ray_o[3 * r + i] = go[i]; p.d_ray_d[3 * r + i] = gd[i]; }
 }
 
 #include "lrt_backward.inc"
@@ -1716,7 +1735,7 @@ static int forward_impl(lrt_state* st, int H, int W, const float* ray_o, const f
 static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const float* ray_d, int P, int M, int deg,
                          const float* means, const float* scales, const float* rots, const float* opac, const float* shs,
                          const float* bg, const float* out9, const float* dL_dout9, float* d_means, float* d_shs,
-                         float* d_opac, float* d_scales, float* d_rots, float* accum_out, void* stream_);
+                         float* d_opac, float* d_scales, float* d_rots, float* accum_out, float* d_ray_o, float* d_ray_d, void* stream_);
 int lrt_backward_accum(lrt_state* st, int H, int W, const float* ray_o, const float* ray_d, int P, int M, int deg,
                        const float* means, const float* scales, const float* rots, const float* opac, const float* shs,
                        const float* bg, const float* out9, const float* dL_dout9, float* d_means, float* d_shs,
@@ -1725,7 +1744,21 @@ int lrt_backward_accum(lrt_state* st, int H, int W, const float* ray_o, const fl
     if (!st) LRT_FAIL(LRT_ERR_ARG, "lrt_backward: null state");
     DeviceGuard dg(st->device);
     rec_begin(st, stream_);
-    return rec_end(st, backward_impl(st, H, W, ray_o, ray_d, P, M, deg, means, scales, rots, opac, shs, bg, out9, dL_dout9, d_means, d_shs, d_opac, d_scales, d_rots, accum_out, stream_),
+    return rec_end(st, backward_impl(st, H, W, ray_o, ray_d, P, M, deg, means, scales, rots, opac, shs, bg, out9, dL_dout9, d_means, d_shs, d_opac, d_scales, d_rots, accum_out,
+                                     nullptr, nullptr, stream_),
+                   (hipStream_t)stream_);
+}
+int lrt_backward_rays(lrt_state* st, int H, int W, const float* ray_o, const float* ray_d, int P, int M, int deg,
+                      const float* means, const float* scales, const float* rots, const float* opac, const float* shs,
+                      const float* bg, const float* out9, const float* dL_dout9, float* d_means, float* d_shs,
+                      float* d_opac, float* d_scales, float* d_rots, float* accum_out, float* d_ray_o, float* d_ray_d, void* stream_)
+{
+    if (!st) LRT_FAIL(LRT_ERR_ARG, "lrt_backward_rays: null state");
+    if ((d_ray_o == nullptr) != (d_ray_d == nullptr)) LRT_FAIL(LRT_ERR_ARG, "lrt_backward_rays: pass both ray gradient pointers or neither");
+    DeviceGuard dg(st->device);
+    rec_begin(st, stream_);
+    return rec_end(st, backward_impl(st, H, W, ray_o, ray_d, P, M, deg, means, scales, rots, opac, shs, bg, out9, dL_dout9, d_means, d_shs, d_opac, d_scales, d_rots, accum_out,
+                                     d_ray_o, d_ray_d, stream_),
                    (hipStream_t)stream_);
 }
 int lrt_backward(lrt_state* st, int H, int W, const float* ray_o, const float* ray_d, int P, int M, int deg,
@@ -1742,7 +1775,7 @@ int lrt_backward(lrt_state* st, int H, int W, const float* ray_o, const float* r
 static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const float* ray_d, int P, int M, int deg,
                          const float* means, const float* scales, const float* rots, const float* opac, const float* shs,
                          const float* bg, const float* out9, const float* dL_dout9, float* d_means, float* d_shs,
-                         float* d_opac, float* d_scales, float* d_rots, float* accum_out, void* stream_)
+                         float* d_opac, float* d_scales, float* d_rots, float* accum_out, float* d_ray_o, float* d_ray_d, void* stream_)
 {
     int rc = check_common("lrt_backward", st, H, W, P, M, deg);
     if (rc) return rc;
@@ -1750,8 +1783,17 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
     if (!bg) LRT_FAIL(LRT_ERR_ARG, "lrt_backward: null background pointer");
     if (P > 0 && (!means || !scales || !rots || !opac || !shs || !d_means || !d_shs || !d_opac || !d_scales || !d_rots))
         LRT_FAIL(LRT_ERR_ARG, "lrt_backward: null parameter/gradient pointer");
+    const bool rays = d_ray_o != nullptr;
+    if (rays && (st->bwd_mode == 1 || st->bwd_mode == 2))
+        LRT_FAIL(LRT_ERR_STATE, "lrt_backward_rays: ray gradients exist for bwd_mode 3 (bucketed replay) and 0 (re-trace), not for bwd_mode %d", st->bwd_mode);
     DeviceGuard dg(st->device);
     hipStream_t stream = (hipStream_t)stream_;
+    // ray gradients: cleared here, stream-ordered; every ray with a composited hit is then stored by exactly one owner (k_bwd_prep2<1>, the
+    // re-trace or the near-ray replay), rays without one stay zero
+    if (rays && (size_t)H * W > 0) {
+        HIPCHK(lrt_memset_async(st->lrec, d_ray_o, 0, (size_t)H * W * 3 * sizeof(float), stream));
+        HIPCHK(lrt_memset_async(st->lrec, d_ray_d, 0, (size_t)H * W * 3 * sizeof(float), stream));
+    }
     // trace_surfels.cpp:322-329: gradients start from zero.  Every path but the bucketed reduction (which stores all rows whole) adds
     // into the tensors, so they are cleared first; adjacent buffers (the Python binding and the sharded path hand over views of one
     // flat tensor) are filled at once
@@ -1776,6 +1818,7 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
     tp.out9_in = out9; tp.dL_dout = dL_dout9; tp.prezeroed = st->grads_prezeroed;
     tp.d_means = d_means; tp.d_shs = d_shs; tp.d_opac = d_opac; tp.d_scales = d_scales; tp.d_rots = d_rots;
     tp.accum = accum_out;                                       // non-null (option deferred_accum): every path below also writes the per-Gaussian sums of composite weights
+    tp.d_ray_o = d_ray_o; tp.d_ray_d = d_ray_d;
     // the re-tracing backward finds the rays with a quad closer than 0.2 m itself and replays them like k_fwd_near does (lrt_near.inc)
     if (st->near_list && (size_t)H * W <= st->near_cap) { tp.near_list = st->near_list + st->near_cap; tp.near_count = st->ctrl + 24; tp.near_done = st->ctrl + 25; tp.naos = (const float*)st->nodes_aos; }
     if (st->hits_valid && st->replay_enabled && st->hit_H == H && st->hit_W == W) {
@@ -1816,7 +1859,8 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
             // a gradient row goes out with one lane per component (bk_row_out): 10 + 3 M <= 64, i.e. M <= 18; wider SH tables (M = 25 with an
             // active degree <= 3) take the sorted path, which zero-fills the tensors first
             const bool bucket = bk_nb > 0 && bk_nb <= BK_MAX_NB && ((unsigned long long)H * W) < (1ull << (32 - bk_shift)) && tp.n_tiles > 0 && (spec || n_hits > 0) && 10 + 3 * M + (accum_out ? 1 : 0) <= 64
-                                && (LRT_HAS_LEGACY || st->fast_valid);      // (the product's per-ray preparation reads the colour pass's record: k_bwd_prep2)
+                                && (LRT_HAS_LEGACY || st->fast_valid)       // (the product's per-ray preparation reads the colour pass's record: k_bwd_prep2)
+                                && (!rays || st->fast_valid);               // (so does its ray-gradient pass)
             if (!bucket) { rc = zero_grads(); if (rc) return rc; }
             if (bucket) {
                 ScopedTimer tm(st, 2, stream);
@@ -1864,17 +1908,18 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
                 if (tp.zero_in_prep && st->zero_in_prep == 2 && (reinterpret_cast<uintptr_t>(d_shs) & 15u) == 0 && (((size_t)P * M * 3) & 3u) == 0) tp.zero_in_prep = 2;
                 if (lds_nb > 48 * 1024) {
                     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bk_count), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nb));
-                    if (tp.fast_prep) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_prep2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nb));
+                    if (tp.fast_prep) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_prep2<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nb));
 #ifdef LRT_LEGACY
                     else HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_bwd_prep<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nb));
 #endif
                 }
                 lrt_launch(st->lrec, k_bk_count, dim3(ng), dim3(256), lds_nb, stream, tp);
                 lrt_launch(st->lrec, k_bk_scan, dim3((unsigned)((bk_nb + 63) / 64), BK_RB), dim3(1024), 0, stream, tp);
-                if (tp.fast_prep) lrt_launch(st->lrec, k_bwd_prep2, dim3(ng), dim3(1024), lds_nb, stream, tp);     // hit_pk keeps the forward's colours: a second backward may use them again
+                if (tp.fast_prep) lrt_launch(st->lrec, k_bwd_prep2<0>, dim3(ng), dim3(1024), lds_nb, stream, tp);     // hit_pk keeps the forward's colours: a second backward may use them again
 #ifdef LRT_LEGACY
                 else lrt_launch(st->lrec, (k_bwd_prep<false, true>), dim3(ng), dim3(1024), lds_nb, stream, tp);
 #endif
+                if (tp.d_ray_o) lrt_launch(st->lrec, k_bwd_prep2<1>, dim3(ng), dim3(1024), 0, stream, tp);     // ray gradients: the same replay once more, per ray (fast_prep: see `bucket`)
                 lrt_launch(st->lrec, k_bk_sort, dim3((unsigned)bk_nb), dim3(256), lds_sort + (tp.det_bm_words ? ((size_t)tp.det_bm_words + 256) * sizeof(unsigned) : 0), stream, tp);
                 if (tp.deterministic) tp.brec2 = st->brec;      // k_bk_sort's second pass left the records, every run in ray order, in the bucket's (dead) span of brec
                 lrt_launch(st->lrec, k_bwd_reduce4, dim3((unsigned)(((size_t)st->key_cap + 255) / 256)), dim3(256), 0, stream, tp);
@@ -1888,6 +1933,7 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
                 return LRT_OK;
             }
 #ifdef LRT_LEGACY      // bwd_mode 1 (replay + atomics) and 2 (sorted reduction): the cross-check library only
+            if (rays) { tp.guard = 0; tp.n_hits_dev = nullptr; return launch_trace(st, tp, true, stream); }     // (they have no ray gradients: re-trace)
             if (tp.n_tiles > 0 && !sorted) {
                 ScopedTimer tm(st, 2, stream);
                 lrt_launch(st->lrec, k_bwd_replay<true>, dim3((tp.n_tiles + 3) / 4), dim3(256), 0, stream, tp);

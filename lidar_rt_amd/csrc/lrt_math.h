@@ -216,6 +216,63 @@ LRT_HD void lrt_hit_backward(const LrtHitGeom* h, const float* o, const float* d
     g->d_rot[3] = 2.f * (x * (dR0[2] + dR2[0]) + y * (dR1[2] + dR2[1]) - 2.f * z * (dR0[0] + dR1[1]) + qw * (dR0[1] - dR1[0]));
 }
 
+// Ray part of the backward for ONE composited hit: ADDS dL/do and dL/dd of this hit to dL_do[3], dL_dd[3].
+// The hit point x = o + t d with t = n.(mu - o) / n.d, n = R[:,2]; the hit's loss reaches the ray through (u, v) of x and through t.
+// With dxyz = dL/dx at fixed t and w = (dxyz.d + dL_dD_gs) / n.d, both exactly as lrt_hit_backward forms them:
+//   v = dxyz - w n,   dL/do += v,   dL/dd += t v
+// (dt/do = -n / n.d, dt/dd = -t n / n.d).  The normal's sign (DUAL_VISIABLE) is piecewise constant in o and carries no gradient; the
+// view-dependent colour is added once per ray by lrt_sh_basis_vjp.
+LRT_HD void lrt_hit_ray_backward(const LrtHitGeom* h, const float* d, float t, float dL_dG, float dL_dD_gs, float* dL_do, float* dL_dd)
+{
+    const float* R = h->R; const float* L0 = h->L0; const float* L1 = h->L1;
+    const float u = h->u, v = h->v, G = h->G;
+    const float dL_du = dL_dG * -G * u, dL_dv = dL_dG * -G * v;
+    float dxyz[3];
+    for (int i = 0; i < 3; i++) dxyz[i] = dL_du * L0[i] + dL_dv * L1[i];
+    const float dL_dt = dxyz[0] * d[0] + dxyz[1] * d[1] + dxyz[2] * d[2] + dL_dD_gs;
+    const float R2[3] = {R[2], R[5], R[8]};
+    const float w = dL_dt / (R2[0] * d[0] + R2[1] * d[1] + R2[2] * d[2]);
+    for (int i = 0; i < 3; i++) {
+        const float vi = dxyz[i] - w * R2[i];
+        dL_do[i] += vi;
+        dL_dd[i] += t * vi;
+    }
+}
+
+// Vector-Jacobian product of lrt_sh_basis: ADDS dL/ddir to dL_dd[3] for the upstream dL_db[k], k < (deg+1)^2, including the Jacobian of
+// the normalisation of a non-unit `dir`: dL/ddir = (g - n (n.g)) / |dir| with g = dL/dn and n = dir / |dir|.
+LRT_HD void lrt_sh_basis_vjp(int deg, const float* dir, const float* dL_db, float* dL_dd)
+{
+    if (deg <= 0) return;
+    const float C1 = 0.4886025119029199f;
+    const float nrm = sqrtf(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]), inv = 1.0f / nrm;
+    const float x = dir[0] * inv, y = dir[1] * inv, z = dir[2] * inv;
+    const float* g = dL_db;
+    float gx = -C1 * g[3], gy = -C1 * g[1], gz = C1 * g[2];
+    if (deg > 1) {
+        const float K0 = 1.0925484305920792f, K1 = -1.0925484305920792f, K2 = 0.31539156525252005f, K3 = -1.0925484305920792f,
+                    K4 = 0.5462742152960396f;
+        gx += K0 * y * g[4] - 2.0f * K2 * x * g[6] + K3 * z * g[7] + 2.0f * K4 * x * g[8];
+        gy += K0 * x * g[4] + K1 * z * g[5] - 2.0f * K2 * y * g[6] - 2.0f * K4 * y * g[8];
+        gz += K1 * y * g[5] + 4.0f * K2 * z * g[6] + K3 * x * g[7];
+        if (deg > 2) {
+            const float Q0 = -0.5900435899266435f, Q1 = 2.890611442640554f, Q2 = -0.4570457994644658f, Q3 = 0.3731763325901154f,
+                        Q4 = -0.4570457994644658f, Q5 = 1.445305721320277f, Q6 = -0.5900435899266435f;
+            const float xx = x * x, yy = y * y, zz = z * z;
+            gx += Q0 * 6.0f * x * y * g[9] + Q1 * y * z * g[10] - Q2 * 2.0f * x * y * g[11] - Q3 * 6.0f * x * z * g[12] +
+                  Q4 * (4.0f * zz - 3.0f * xx - yy) * g[13] + Q5 * 2.0f * x * z * g[14] + Q6 * 3.0f * (xx - yy) * g[15];
+            gy += Q0 * 3.0f * (xx - yy) * g[9] + Q1 * x * z * g[10] + Q2 * (4.0f * zz - xx - 3.0f * yy) * g[11] - Q3 * 6.0f * y * z * g[12] -
+                  Q4 * 2.0f * x * y * g[13] - Q5 * 2.0f * y * z * g[14] - Q6 * 6.0f * x * y * g[15];
+            gz += Q1 * x * y * g[10] + Q2 * 8.0f * y * z * g[11] + Q3 * (6.0f * zz - 3.0f * xx - 3.0f * yy) * g[12] +
+                  Q4 * 8.0f * x * z * g[13] + Q5 * (xx - yy) * g[14];
+        }
+    }
+    const float ng = x * gx + y * gy + z * gz;
+    dL_dd[0] += (gx - x * ng) * inv;
+    dL_dd[1] += (gy - y * ng) * inv;
+    dL_dd[2] += (gz - z * ng) * inv;
+}
+
 // Hit distance of the ray (o, d) on the plane of Gaussian g in fp64, from the RAW fp32 parameters as the build packed them
 // ((mean, opacity) (scale, rot.wx) (rot.yz, -, -) per primitive): n = third column of R(q / |q|) (lrt_quat_to_R), t = n.(mu - o) / n.d.
 // Used to order hits that fp32 cannot separate (closer than 2 ulp).

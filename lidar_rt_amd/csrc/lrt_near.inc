@@ -264,7 +264,7 @@ __device__ __forceinline__ void near_replay(const TraceParams& p, const float* _
         int last_g = -1, n_rec = 0, first = 0;
         float b[16];
         if (!defer || BWD) lrt_sh_basis(p.deg, d, b);
-        float N0 = 0.f, N1 = 0.f, N2 = 0.f;
+        float N0 = 0.f, N1 = 0.f, N2 = 0.f, go[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f};
         float dL[LRT_NCH], fin[LRT_NCH], dL_dbg = 0.f;
         if (BWD) {
             for (int i = 0; i < LRT_NCH; i++) { dL[i] = p.dL_dout[LRT_NCH * (size_t)r + i]; fin[i] = p.out9_in[LRT_NCH * (size_t)r + i]; }
@@ -300,9 +300,10 @@ __device__ __forceinline__ void near_replay(const TraceParams& p, const float* _
                 test_T = T * (1.f - alpha);
                 if (test_T < LRT_T_STOP) { brk = true; break; }
                 if (BWD) {                                                           // backward.cu:538-676 on this hit, at the depth the forward used
-                    RayAcc a = {T, C0, C1, C2, Dd, Wt, N0, N1, N2};
+                    RayAcc a = {T, C0, C1, C2, Dd, Wt, N0, N1, N2, {go[0], go[1], go[2]}, {gd[0], gd[1], gd[2]}};
                     bwd_hit<false, true>(p, o, d, b, p.nsh, dL, fin, dL_dbg, dpt, g, 0.f, a);
                     C0 = a.C0; C1 = a.C1; C2 = a.C2; Dd = a.Dd; N0 = a.N0; N1 = a.N1; N2 = a.N2;
+                    for (int i2 = 0; i2 < 3; i2++) { go[i2] = a.go[i2]; gd[i2] = a.gd[i2]; }
                     T = test_T;
                     continue;
                 }
@@ -327,7 +328,7 @@ __device__ __forceinline__ void near_replay(const TraceParams& p, const float* _
             if (test_T < LRT_T_STOP || cnt < (unsigned)LRT_CHUNK) break;
             pdpt = dpt + LRT_STEP_EPS;
         }
-        if (BWD) return;
+        if (BWD) { if (p.d_ray_o) store_ray_grad(p, (size_t)r, go, gd); return; }
         float* op_ = p.out9 + LRT_NCH * (size_t)r;
         if (!defer) { op_[0] = C0 + T * p.bg[0]; op_[1] = C1 + T * p.bg[1]; op_[2] = C2 + T * p.bg[2]; }
         op_[3] = Dd; op_[4] = Wt; op_[5] = 0.f; op_[6] = 0.f; op_[7] = 0.f; op_[8] = T;

@@ -198,7 +198,8 @@ trace_surfels_backward(State& st, const at::Tensor& ray_o, const at::Tensor& ray
                        const at::Tensor& rotations, const c10::optional<at::Tensor>& transMat_precomp, const c10::optional<at::Tensor>& viewmatrix,
                        const c10::optional<at::Tensor>& projmatrix, const c10::optional<at::Tensor>& campos, bool prefiltered, bool debug,
                        const at::Tensor& out_attr_float32, const c10::optional<at::Tensor>& out_attr_uint32, const at::Tensor& dL_dout_attr_float32,
-                       const py::object& grads_out, const py::object& forward_serial, const c10::optional<at::Tensor>& accum_out)
+                       const py::object& grads_out, const py::object& forward_serial, const c10::optional<at::Tensor>& accum_out,
+                       const py::object& ray_grads_out)
 {
     (void)vertices; (void)viewmatrix; (void)projmatrix; (void)campos; (void)prefiltered; (void)debug; (void)out_attr_uint32; (void)scale_modifier;
     const int64_t P = prep(ray_o, ray_d, background, means3D, shs, colors_precomp, opacities, scales, rotations, transMat_precomp);
@@ -242,7 +243,23 @@ trace_surfels_backward(State& st, const at::Tensor& ray_o, const at::Tensor& ray
         TORCH_CHECK(acc.dim() == 1 && acc.size(0) == P && acc.is_contiguous() && acc.scalar_type() == at::kFloat && acc.device() == means3D.device(),
                     "accum_out must be a contiguous float32 device tensor of shape (P,)");
     }
-    {
+    // ray gradients (lrt_backward_rays): (d_ray_o, d_ray_d), contiguous float32 (H, W, 3) device tensors, every element written
+    at::Tensor gro, grd;
+    if (!ray_grads_out.is_none()) {
+        py::tuple t = ray_grads_out.cast<py::tuple>();
+        TORCH_CHECK(t.size() == 2, "ray_grads_out must be a pair (d_ray_o, d_ray_d)");
+        gro = t[0].cast<at::Tensor>(); grd = t[1].cast<at::Tensor>();
+        auto ok = [&](const at::Tensor& x) {
+            return x.dim() == 3 && x.size(0) == H && x.size(1) == W && x.size(2) == 3 && x.is_contiguous() && x.scalar_type() == at::kFloat && x.device() == means3D.device(); };
+        TORCH_CHECK(ok(gro) && ok(grd), "ray_grads_out tensors must be contiguous float32 device tensors of shape (H, W, 3)");
+    }
+    if (gro.defined()) {
+        c10::hip::HIPGuard guard(idx);
+        check_rc(lrt_backward_rays(h, (int)H, (int)W, fptr(ro), fptr(rd), (int)P, (int)M, degree, fptr(m), fptr(s), fptr(r), fptr(o), fptr(sh), fptr(bg),
+                                   fptr(out), fptr(dL), fptr_mut(d_means), fptr_mut(d_shs), fptr_mut(d_opac), fptr_mut(d_scales), fptr_mut(d_rot),
+                                   acc.defined() ? fptr_mut(acc) : nullptr, fptr_mut(gro), fptr_mut(grd), (void*)c10::hip::getCurrentHIPStream(idx).stream()),
+                 "lrt_backward_rays");
+    } else {
         c10::hip::HIPGuard guard(idx);
         check_rc(lrt_backward_accum(h, (int)H, (int)W, fptr(ro), fptr(rd), (int)P, (int)M, degree, fptr(m), fptr(s), fptr(r), fptr(o), fptr(sh), fptr(bg),
                                     fptr(out), fptr(dL), fptr_mut(d_means), fptr_mut(d_shs), fptr_mut(d_opac), fptr_mut(d_scales), fptr_mut(d_rot),
@@ -291,5 +308,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod)
             py::arg("means3D"), py::arg("shs"), py::arg("degree"), py::arg("colors_precomp"), py::arg("opacities"), py::arg("scales"), py::arg("scale_modifier"),
             py::arg("rotations"), py::arg("transMat_precomp"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("campos"), py::arg("prefiltered"),
             py::arg("debug"), py::arg("out_attr_float32"), py::arg("out_attr_uint32"), py::arg("dL_dout_attr_float32"), py::arg("grads_out") = py::none(),
-            py::arg("forward_serial") = py::none(), py::arg("accum_out") = py::none());
+            py::arg("forward_serial") = py::none(), py::arg("accum_out") = py::none(), py::arg("ray_grads_out") = py::none());
 }

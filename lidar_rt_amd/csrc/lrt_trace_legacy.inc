@@ -49,6 +49,7 @@ __global__ void __launch_bounds__(256, 2) k_trace(const TraceParams p, const flo
         lrt_sh_basis(p.deg, d, b);
 
         float T = 1.f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dd = 0.f, Wt = 0.f, N0 = 0.f, N1 = 0.f, N2 = 0.f;
+        float go[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f};      // BWD: the ray's gradient (p.d_ray_o)
         float dL[LRT_NCH], fin[LRT_NCH], dL_dbg = 0.f;
         if (BWD) {
             for (int i = 0; i < LRT_NCH; i++) { dL[i] = p.dL_dout[LRT_NCH * r + i]; fin[i] = p.out9_in[LRT_NCH * r + i]; }
@@ -210,9 +211,10 @@ __global__ void __launch_bounds__(256, 2) k_trace(const TraceParams p, const flo
                                     n_rec++;
                                 }
                             } else {
-                                RayAcc a = {T, C0, C1, C2, Dd, Wt, N0, N1, N2};
+                                RayAcc a = {T, C0, C1, C2, Dd, Wt, N0, N1, N2, {go[0], go[1], go[2]}, {gd[0], gd[1], gd[2]}};
                                 bwd_hit<true, true>(p, o, d, b, nsh, dL, fin, dL_dbg, t, g, ao, a);
                                 C0 = a.C0; C1 = a.C1; C2 = a.C2; Dd = a.Dd; N0 = a.N0; N1 = a.N1; N2 = a.N2;
+                                for (int i2 = 0; i2 < 3; i2++) { go[i2] = a.go[i2]; gd[i2] = a.gd[i2]; }
                             }
                             T = testT;
                         }
@@ -228,6 +230,7 @@ __global__ void __launch_bounds__(256, 2) k_trace(const TraceParams p, const flo
         if (p.stats) { const unsigned long long dc = wall_clock64() - clk0; st_clk_sum += dc; st_clk_max = dc > st_clk_max ? dc : st_clk_max; }
         if (!BWD && valid && is_near) { const unsigned ix = atomicAdd(p.near_count, 1u); p.near_list[ix] = (int)r; n_rec = 0; }
         if (BWD && valid && is_near && p.near_list) { const unsigned ix = atomicAdd(p.near_count, 1u); p.near_list[ix] = (int)r; }      // replayed below
+        if (BWD && valid && !is_near && p.d_ray_o) store_ray_grad(p, r, go, gd);                                                  // (a near ray: by the replay)
         if (!BWD && valid && p.hit_t) {
             p.hit_n[r] = min(n_rec, p.hit_cap); if (n_rec > p.hit_cap) atomicOr(p.hit_ovf, 1);
             if (p.hit_count) atomicAdd(p.hit_count, (unsigned)min(n_rec, p.hit_cap));     // no return value: fire and forget

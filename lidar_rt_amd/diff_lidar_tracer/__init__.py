@@ -33,7 +33,8 @@ class TracingSettings(NamedTuple):
 
 class _Tracer(torch.autograd.Function):
     """Inputs 5..12 (means3D, grads3D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-    receive gradients; ray_o, ray_d and vertices do not (reference :119-134)."""
+    receive gradients (reference :119-134); ray_o and ray_d too when they require it (addition: lrt_backward_rays, dense
+    (H, W, 3) gradients -- an expanded ray_o view reaches its source through autograd's expand backward); vertices do not."""
 
     @staticmethod
     def forward(ctx, state, training, ray_o, ray_d, vertices, means3D, grads3D, shs, colors_precomp, opacities,
@@ -62,14 +63,22 @@ class _Tracer(torch.autograd.Function):
         ts = ctx.tracer_settings
         (ray_o, ray_d, vertices, means3D, shs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
          out_f32, out_i32) = ctx.saved_tensors
+        want_o, want_d = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        ray_grads = None
+        if want_o or want_d:
+            H, W = ray_o.shape[0], ray_o.shape[1]
+            ray_grads = tuple(torch.empty((H, W, 3), dtype=torch.float32, device=means3D.device) for _ in range(2))
         (g_means, g_shs, g_colors, g_opac, g_scales, g_rot, g_cov, g_g3) = _C.trace_surfels_backward(
             ctx.state, ray_o, ray_d, vertices, ts.bg, means3D, shs, ts.sh_degree, colors_precomp, opacities, scales,
             ts.scale_modifier, rotations, cov3Ds_precomp, ts.viewmatrix, ts.projmatrix, ts.campos, ts.prefiltered,
-            ts.debug, out_f32, out_i32, grad_out_f32, forward_serial=ctx.forward_serial, accum_out=ctx.accum_out)
+            ts.debug, out_f32, out_i32, grad_out_f32, forward_serial=ctx.forward_serial, accum_out=ctx.accum_out,
+            ray_grads_out=ray_grads)
         g_opac = g_opac.reshape(opacities.shape)
         g_colors = g_colors if colors_precomp.numel() > 0 else None
         g_cov = g_cov if cov3Ds_precomp.numel() > 0 else None
-        return (None, None, None, None, None, g_means, g_g3, g_shs, g_colors, g_opac, g_scales, g_rot, g_cov, None, None)
+        g_ro = ray_grads[0].to(ray_o.dtype) if want_o else None
+        g_rd = ray_grads[1].to(ray_d.dtype) if want_d else None
+        return (None, None, g_ro, g_rd, None, g_means, g_g3, g_shs, g_colors, g_opac, g_scales, g_rot, g_cov, None, None)
 
 
 class Tracer(nn.Module):
@@ -123,8 +132,9 @@ class Tracer(nn.Module):
         # reads.  With a backward to follow (training mode, grad mode on, some input requires a gradient) nothing waits here; without
         # one the host waits for the trace and raises now -- unless `deferred_checks` is set (evaluation loops: render many frames,
         # then call `check()` once).
+        # (rays that require grad count too: a pose-only loop with frozen Gaussians records its hits and replays them)
         will_backward = self.training and torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad for t in (means3D, grads3D, shs, opacities, scales, rotations))
+            t is not None and t.requires_grad for t in (means3D, grads3D, shs, opacities, scales, rotations, ray_o, ray_d))
         check_now = not will_backward and not self.deferred_checks
         return _Tracer.apply(self.optix_context, self.training and will_backward, ray_o, ray_d, vertices, means3D, grads3D, shs,
                              colors_precomp, opacities, scales, rotations, cov3Ds_precomp, tracer_settings, check_now)

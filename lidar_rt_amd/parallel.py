@@ -412,6 +412,9 @@ class ShardedTracer:
         self.cull_readbacks += 1 if g is None else 0
 
     def forward(self, ray_o, ray_d, means, scales, rotations, opacities, shs, deg, bg, mod=1.0, rebuild=True, cull_key=None):
+        if torch.is_grad_enabled() and (ray_o.requires_grad or ray_d.requires_grad):
+            raise ValueError("ShardedTracer: ray gradients (rays that require grad) are not supported under azimuth sharding; "
+                             "use diff_lidar_tracer.Tracer")
         H, W = ray_o.shape[:2]
         self._dev = means.device
         if self.world > 1 or self.force_collectives:

@@ -1,0 +1,119 @@
+"""Sensor pose refinement: one se(3) correction per frame, learnt through the tracer's ray gradients (lrt_backward_rays).
+
+``SensorPoses(frames, frame_ids)`` holds xi = (rho, phi) per frame, zero-initialised; the corrected pose is ``sensor2world @ Exp(xi)``
+(a correction in the sensor frame).  The rays are rebuilt from it by ``RangeFrames.range_rays`` -- differentiable torch -- so that
+``loss.backward()`` carries dL/dray_o and dL/dray_d from the tracer back to xi.  The object is duck-typed as a sensor for
+``renderer.raytracing`` (``get_range_rays``, ``sensor_center``, ``inverse_projection_with_range``, the ground-truth accessors of
+``frames``) and brings its own Adam optimiser with separate translation / rotation learning rates (``step()`` / ``zero_grad()``).
+"""
+from __future__ import annotations
+
+from typing import Dict, Iterable, Optional
+
+import torch
+
+
+def _hat(v: torch.Tensor) -> torch.Tensor:
+    z = torch.zeros((), dtype=v.dtype, device=v.device)
+    return torch.stack([torch.stack([z, -v[2], v[1]]), torch.stack([v[2], z, -v[0]]), torch.stack([-v[1], v[0], z])])
+
+
+def se3_exp(xi: torch.Tensor) -> torch.Tensor:
+    """(6,) xi = (rho, phi) -> (4, 4) SE(3) matrix.  Rodrigues with the small-angle series below 1e-4 rad: autograd of |phi| at exactly
+    phi = 0 is NaN, and the zero-initialised corrections start there."""
+    rho, phi = xi[:3], xi[3:]
+    th2 = (phi * phi).sum()
+    small = th2 < 1e-8
+    th2s = torch.where(small, torch.ones_like(th2), th2)                  # keeps the unused branch finite (and its gradient)
+    th = torch.sqrt(th2s)
+    A = torch.where(small, 1.0 - th2 / 6.0, torch.sin(th) / th)                             # sin t / t
+    B = torch.where(small, 0.5 - th2 / 24.0, (1.0 - torch.cos(th)) / th2s)                  # (1 - cos t) / t^2
+    C = torch.where(small, 1.0 / 6.0 - th2 / 120.0, (th - torch.sin(th)) / (th2s * th))     # (t - sin t) / t^3
+    K = _hat(phi)
+    I = torch.eye(3, dtype=xi.dtype, device=xi.device)
+    K2 = K @ K
+    R = I + A * K + B * K2
+    V = I + B * K + C * K2
+    top = torch.cat([R, (V @ rho).unsqueeze(1)], 1)
+    bottom = torch.tensor([[0.0, 0.0, 0.0, 1.0]], dtype=xi.dtype, device=xi.device)
+    return torch.cat([top, bottom], 0)
+
+
+class SensorPoses:
+    def __init__(self, frames, frame_ids: Optional[Iterable[int]] = None, lr_trans: float = 1e-3, lr_rot: float = 1e-3):
+        meta = getattr(frames, "pose_meta", {})
+        ids = list(frame_ids) if frame_ids is not None else list(frames.train_frames)
+        for f in ids:
+            if f not in meta:
+                raise ValueError(f"SensorPoses: frame {f} was added as plain rays (RangeFrames.add_frame); only frames added with "
+                                 "add_range_image (inclination + sensor2world) can be refined")
+        self.frames = frames
+        self.frame_ids = ids
+        dev = frames.depth[ids[0]].device if ids else torch.device("cpu")
+        self.xi: Dict[int, torch.nn.Parameter] = {f: torch.nn.Parameter(torch.zeros(6, dtype=torch.float32, device=dev)) for f in ids}
+        self.optimizer = torch.optim.Adam([{"params": list(self.xi.values()), "lr": 1.0, "name": "xi"}], betas=(0.9, 0.999), eps=1e-15)
+        self.lr_trans, self.lr_rot = float(lr_trans), float(lr_rot)
+
+    # ---- the corrected poses ---------------------------------------------------------------------------------------------------
+    def sensor2world(self, frame) -> torch.Tensor:
+        """(4, 4) corrected pose, differentiable in xi[frame]."""
+        inc, s2w, _, _ = self.frames.pose_meta[frame]
+        return s2w.to(torch.float32) @ se3_exp(self.xi[frame])
+
+    def get_range_rays(self, frame):
+        inc, s2w, data_type, s2e = self.frames.pose_meta[frame]
+        H, W = self.frames.depth[frame].shape[:2]
+        return self.frames.range_rays(H, W, inc, self.sensor2world(frame), data_type, s2e)
+
+    @property
+    def sensor_center(self):
+        return _Centers(self)
+
+    def inverse_projection_with_range(self, frame, range_map, mask=None):
+        o, d = self.get_range_rays(frame)
+        pts = (o + d * range_map.reshape(*d.shape[:2], 1)).reshape(-1, 3)
+        if mask is None:
+            return pts.index_select(0, self.frames.mask_index[frame])
+        return pts[mask.reshape(-1).bool()]
+
+    # the ground truth: the frames' own
+    train_frames = property(lambda s: s.frame_ids)
+    get_depth = lambda s, f: s.frames.get_depth(f)
+    get_intensity = lambda s, f: s.frames.get_intensity(f)
+    get_mask = lambda s, f: s.frames.get_mask(f)
+    mask_index = property(lambda s: s.frames.mask_index)
+
+    # ---- optimisation ------------------------------------------------------------------------------------------------------------
+    def zero_grad(self):
+        self.optimizer.zero_grad(set_to_none=True)
+
+    @torch.no_grad()
+    def step(self):
+        """One Adam step; the translation (rho) and rotation (phi) parts of xi have their own learning rates (Adam's update is
+        elementwise, so scaling a unit-rate step per component is exactly two learning rates)."""
+        before = {f: x.detach().clone() for f, x in self.xi.items()}
+        self.optimizer.step()
+        scale = torch.tensor([self.lr_trans] * 3 + [self.lr_rot] * 3, device=next(iter(self.xi.values())).device)
+        for f, x in self.xi.items():
+            x.copy_(before[f] + (x - before[f]) * scale)
+
+    def state_dict(self):
+        return {"xi": {f: x.detach().cpu() for f, x in self.xi.items()}, "optimizer": self.optimizer.state_dict(),
+                "lr_trans": self.lr_trans, "lr_rot": self.lr_rot}
+
+    def load_state_dict(self, sd):
+        with torch.no_grad():
+            for f, x in sd["xi"].items():
+                self.xi[f].copy_(x.to(self.xi[f].device))
+        self.optimizer.load_state_dict(sd["optimizer"])
+        self.lr_trans, self.lr_rot = float(sd["lr_trans"]), float(sd["lr_rot"])
+
+
+class _Centers:
+    """``sensor_center[frame]``: the corrected sensor position."""
+
+    def __init__(self, poses: SensorPoses):
+        self.p = poses
+
+    def __getitem__(self, frame):
+        return self.p.sensor2world(frame)[:3, 3]

@@ -152,6 +152,8 @@ def raytracing(frame, gaussian_assets, sensor, background, args, scaling_modifie
     except Exception:
         pass
     if sharded is not None:
+        if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+            raise ValueError("renderer.sharded: ray gradients (e.g. sensor pose refinement) are not supported under azimuth sharding")
         # this rank's azimuth slab + collectives (build, trace and exchange inside ShardedTracer); same outputs on every rank
         accum = torch.zeros(means3D.shape[0], dtype=torch.float32, device=means3D.device)
         rendered = _ShardedTrace.apply(sharded, rays_o, rays_d, means3D, scales, rotations, opacity, shs,

@@ -63,10 +63,18 @@ def run(args) -> dict:
     scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed)
     scene.training_setup(opt)
     first = 1
+    sensor_poses = None
+    if args.refine_poses:
+        # one se(3) correction per training frame, learnt through the tracer's ray gradients (lidar_rt_amd.poses); saved beside each checkpoint
+        from .poses import SensorPoses
+        sensor_poses = SensorPoses(seq.frames, seq.train_frames, lr_trans=args.pose_lr_trans, lr_rot=args.pose_lr_rot)
     if args.resume:
         model_params, it0 = torch.load(args.resume, map_location=dev, weights_only=False)
         scene.restore(model_params, opt)
         first = int(it0) + 1
+        pp = os.path.join(os.path.dirname(os.path.abspath(args.resume)), f"poses{int(it0)}.pth")
+        if sensor_poses is not None and os.path.exists(pp):
+            sensor_poses.load_state_dict(torch.load(pp, map_location=dev, weights_only=False))
     os.makedirs(args.out, exist_ok=True)
     bg = torch.tensor([0.0, 0.0, 1.0], device=dev)       # the reference's background for (intensity, ray-hit, ray-drop): train.py:106
     log, t0 = [], time.perf_counter()
@@ -74,7 +82,7 @@ def run(args) -> dict:
     for it in range(first, args.iters + 1):
         torch.manual_seed(args.seed * 1_000_003 + it)      # the densification's random draws: a function of (seed, iteration) on every rank
         frame = frame_of(args.seed, it, seq.train_frames)
-        res = training.training_step(scene, seq.frames, frame, it, opt, bg, dynamic=bool(seq.meta.get("dynamic")))
+        res = training.training_step(scene, seq.frames, frame, it, opt, bg, dynamic=bool(seq.meta.get("dynamic")), poses=sensor_poses)
         if it % args.log_every == 0 or it == args.iters:
             row = {"iteration": it, "frame": int(frame), "loss": float(res["loss"]), "depth": float(res["depth"]), "intensity": float(res["intensity"]),
                    "raydrop": float(res["raydrop"]), "points": int(res["points"]), "seconds": round(time.perf_counter() - t0, 3)}
@@ -83,6 +91,8 @@ def run(args) -> dict:
                 print(json.dumps(row), flush=True)
         if rank == 0 and (it % args.save_every == 0 or it == args.iters):
             scene.save(it, os.path.join(args.out, f"chkpnt{it}.pth"))
+            if sensor_poses is not None:
+                torch.save(sensor_poses.state_dict(), os.path.join(args.out, f"poses{it}.pth"))
     if renderer.sharded is not None:
         renderer.sharded.check(wait=True)
     elif renderer.tracer_2dgs is not None:
@@ -91,7 +101,7 @@ def run(args) -> dict:
     if world > 1:
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()
-    return {"log": log, "scene": scene, "sequence": seq, "last": res}
+    return {"log": log, "scene": scene, "sequence": seq, "last": res, "poses": sensor_poses}
 
 
 def main(argv=None) -> int:
@@ -111,7 +121,13 @@ def main(argv=None) -> int:
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (Tracer(deterministic=True): the backward adds a Gaussian's records up by ray and "
                     "the pieces of long runs in order, the forward keeps no learnt tables): ~1.4 x the tracer time; a run resumed from a checkpoint then equals the "
                     "uninterrupted one bit for bit (with lambda_cd = 0: the Chamfer backward adds with float atomics)")
+    ap.add_argument("--refine-poses", action="store_true", help="also learn a per-frame se(3) correction of the recorded sensor poses through the tracer's "
+                    "ray gradients (lidar_rt_amd.poses); written as poses<it>.pth beside each checkpoint and read back by --resume")
+    ap.add_argument("--pose-lr-trans", type=float, default=1e-3, help="--refine-poses: Adam learning rate of the translation part (m)")
+    ap.add_argument("--pose-lr-rot", type=float, default=1e-4, help="--refine-poses: Adam learning rate of the rotation part (rad)")
     args = ap.parse_args(argv)
+    if args.refine_poses and args.gpus > 1:
+        ap.error("--refine-poses needs ray gradients, which azimuth sharding (--gpus > 1) does not provide")
     if args.exact_accum and args.deterministic:
         ap.error("--deterministic takes the hit weights from the backward (the forward's are float atomics): not with --exact-accum")
     if args.out is None:

@@ -357,6 +357,7 @@ class RangeFrames:
         self.mask: Dict[int, torch.Tensor] = {}
         self.mask_index: Dict[int, torch.Tensor] = {}
         self.sensor_center: Dict[int, torch.Tensor] = {}
+        self.pose_meta: Dict[int, tuple] = {}     # frames added by add_range_image: (inclination, sensor2world, data_type, sensor2ego) -- poses.SensorPoses
 
     @staticmethod
     def range_rays(H: int, W: int, inclination, sensor2world: torch.Tensor, data_type: str = "KITTI",
@@ -390,6 +391,7 @@ class RangeFrames:
         """A frame given as range image + sensor pose (what the reference's loaders put into LiDARSensor)."""
         o, d = self.range_rays(depth.shape[0], depth.shape[1], inclination, sensor2world, data_type, sensor2ego)
         self.add_frame(frame, o, d, depth, intensity, mask)
+        self.pose_meta[frame] = (inclination, sensor2world, data_type, sensor2ego)
 
     def add_frame(self, frame, rays_o, rays_d, depth, intensity, mask):
         self.rays[frame] = (rays_o, rays_d)
@@ -449,9 +451,10 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11) -> torch
 
 
 def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: int, opt, background: torch.Tensor,
-                  dynamic: bool = False, chamfer_points_detached: bool = True) -> Dict[str, torch.Tensor]:
+                  dynamic: bool = False, chamfer_points_detached: bool = True, poses=None) -> Dict[str, torch.Tensor]:
     """One iteration of train.py:125-220: render, depth L1 + intensity L1/L2/DSSIM + ray-drop BCE + Chamfer + box
     regularisation, backward, then ``scene.optimize`` with ``means3D.grad`` and the accumulated hit weights.
+    ``poses`` (a ``poses.SensorPoses`` over ``frames``): render through its corrected poses and take its optimiser step after the backward.
     ``chamfer_points_detached``: the reference builds both point clouds from numpy (lidar_sensor.py:182-183), so its
     Chamfer term carries no gradient; False keeps the predicted points differentiable."""
     from .renderer import raytracing
@@ -463,9 +466,13 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
     args = SimpleNamespace(dynamic=dynamic, opt=opt, pipe=SimpleNamespace())
     from . import renderer as _rnd
 
+    sensor = frames if poses is None else poses
+    if poses is not None:
+        poses.zero_grad()
+
     def attempt():
         """render -> losses -> backward (train.py:148-214); everything the optimizer step reads afterwards"""
-        pkg = raytracing(frame, scene.gaussians_assets, frames, background, args)
+        pkg = raytracing(frame, scene.gaussians_assets, sensor, background, args)
         depth, intensity, raydrop = pkg["depth"].squeeze(-1), pkg["intensity"].squeeze(-1), pkg["raydrop"]
         mask = frames.get_mask(frame)
         gt_depth, gt_int = frames.get_depth(frame), frames.get_intensity(frame)
@@ -482,8 +489,8 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
         loss_drop = opt.lambda_raydrop_bce * F.binary_cross_entropy(raydrop.reshape(-1, 1).clamp(1e-7, 1 - 1e-7), labels)
         if opt.lambda_cd != 0:
             pred_depth = depth.detach() if chamfer_points_detached else depth
-            gt_pts = frames.inverse_projection_with_range(frame, gt_depth)
-            pred_pts = frames.inverse_projection_with_range(frame, pred_depth)
+            gt_pts = sensor.inverse_projection_with_range(frame, gt_depth)
+            pred_pts = sensor.inverse_projection_with_range(frame, pred_depth)
             d1, d2, _, _ = chamfer_3DDist()(pred_pts[None].contiguous(), gt_pts[None].contiguous())
             loss_cd = opt.lambda_cd * (d1 + d2).mean() * 0.5
         else:                                                             # weight 0: the term (and its HIP operator) is skipped
@@ -518,6 +525,9 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
                                "the optimizer step was NOT taken, the parameters are those of the previous iteration.  " + _rnd.sharded._STATUS_HELP)
     with torch.no_grad():
         info = scene.optimize(opt, iteration, pkg["means3D"].grad, pkg["accum_gaussian_weight"])
+    if poses is not None:
+        poses.step()
+    with torch.no_grad():
         # multi-GPU: the replicas are never synchronised (identical gradients + identical seeds keep them identical); verify it now and then
         k_chk = int(getattr(opt, "replica_check_interval", 500))
         if _rnd.sharded is not None and k_chk > 0 and iteration % k_chk == 0:
