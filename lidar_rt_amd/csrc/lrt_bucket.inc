@@ -215,11 +215,9 @@ __global__ void __launch_bounds__(256) k_bk_sort(const TraceParams p)
     }
     if (p.prezeroed || p.zero_in_prep) return;             // the caller keeps the tensors all-zero between steps / k_bwd_prep2 cleared them whole: nothing to clear
     const int M3 = 3 * p.M, nrow = 10 + M3;
+    // (option deferred_accum: the lane behind the row clears the weight too -- the tensor the caller hands over may hold anything, e.g. the
+    // sharded tracer's reused exchange buffer; the default, zero_in_prep, never gets here)
     const BkRowLane rl = bk_row_lane(p, lane, nrow, M3);
-    // (option deferred_accum: the weight column of a Gaussian WITHOUT a hit is zero already -- the forward's prologue cleared the tensor -- so
-    // only the rows the reduction adds onto with atomics get their weight cleared here: 800 k scattered 4-byte stores per S1M frame otherwise)
-    BkRowLane rl_nohit = rl;
-    if (lane == nrow) rl_nohit.base = nullptr;
     for (int gb = wv * 64; gb < Gb; gb += 256) {
         const int gq = gb + lane;
         bool z = false, cross = false;
@@ -228,10 +226,9 @@ __global__ void __launch_bounds__(256) k_bk_sort(const TraceParams p)
             cross = (a != e) && ((a >> 6) != ((e - 1u) >> 6));
             z = (a == e) || cross;
         }
-        const unsigned long long crossm = __ballot(cross);
         for (unsigned long long rest = __ballot(z); rest; rest &= rest - 1ull) {
             const int j = __builtin_ctzll(rest);
-            bk_row_out(((crossm >> j) & 1ull) ? rl : rl_nohit, (size_t)g0 + gb + j, 0.f, false);
+            bk_row_out(rl, (size_t)g0 + gb + j, 0.f, false);
         }
     }
 }

@@ -234,7 +234,7 @@ struct lrt_state {
     long long fwd_serial; // incremented by every lrt_forward: identifies which forward the hit record belongs to
     // stream-ordered backward: when the forward's status words have not reached the host yet, the backward is enqueued with sizes
     // SPECULATED from the last completed forward of the same image size (est_hits x 1.125 + 64 k) and decides on the device
-    int spec_bwd; int est_valid, est_pending; unsigned est_hits; size_t est_hw, pend_hw; int* status_dev; int bwdq_fresh, last_bwd_spec, spec_margin, defer_errors; hipStream_t last_stream; int* near_list; size_t near_cap;
+    int spec_bwd; int est_valid, est_pending; unsigned est_hits; size_t est_hw, pend_hw; int* status_dev; int bwdq_fresh, last_bwd_spec, last_bwd_path, spec_margin, defer_errors; hipStream_t last_stream; int* near_list; size_t near_cap;
     int fwd_mode;        // 1 = collect & resolve (default), 0 = legacy 16-slot K-buffer packets
     int tile16_w_log2; float slab0; int* err_flag; float* cr_lists; int cr_blocks_cap; int wg4_per_cu; int c4_qlimit; int fwd_pending; int c4_waves; float* tile_w0; int tile_w0_n; int tile_w0_key[3]; int learn_slab; int root_nodes; int lpt; int tile_cost_ready; int bk_columns;
     // One learnt tile table (first-slab widths, tile lengths, queue boundaries) PER RAY SET: option ray_set names the set the next forwards trace (a training loop's
@@ -893,7 +893,7 @@ int lrt_get_option(lrt_state* st, const char* name, int* value)
 {
     if (!st || !name || !value) LRT_FAIL(LRT_ERR_ARG, "lrt_get_option: null argument");
     const struct { const char* n; int v; } tab[] = {{"hit_cap", st->hit_cap}, {"hit_cap_auto", st->hit_cap_auto}, {"fwd_mode", st->fwd_mode},
-        {"bwd_mode", st->bwd_mode}, {"reduce_mode", st->reduce_mode}, {"defer_colour", st->defer_colour}, {"c4_waves", st->c4_waves}, {"spec_bwd", st->spec_bwd}, {"last_bwd_speculative", st->last_bwd_spec},
+        {"bwd_mode", st->bwd_mode}, {"reduce_mode", st->reduce_mode}, {"defer_colour", st->defer_colour}, {"c4_waves", st->c4_waves}, {"spec_bwd", st->spec_bwd}, {"last_bwd_speculative", st->last_bwd_spec}, {"last_bwd_path", st->last_bwd_path},
         {"graph", st->graph_mode}, {"deferred_accum", st->deferred_accum}, {"deterministic", st->deterministic}, {"carry_order", st->carry}, {"carry_age", st->carry_age}, {"carry_inversions_last", (int)st->carry_inv_last}, {"graph_hits", (int)(st->lrec->hits & 0x7fffffff)}, {"graph_captures", (int)(st->lrec->captures & 0x7fffffff)}};
     for (const auto& e : tab) if (!strcmp(name, e.n)) { *value = e.v; return LRT_OK; }
     if (!strcmp(name, "cull_last")) {                        // primitives the last culled build kept (raw: also those a too small speculative size lost); -1 = none yet
@@ -1829,7 +1829,9 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
         // the re-tracing fallback (enqueued behind it, returns at once when not needed).  Only the first backward of an image size
         // waits for the forward.
         bool ready = hipEventQuery(st->hit_ev) == hipSuccess;
-        const bool can_spec = st->spec_bwd && st->bwd_mode >= 2 && st->est_valid && st->est_hw == (size_t)H * W && st->key_cap > 0;
+        // (option deterministic: never speculated -- a record that turns out unusable would fall back to the float-atomic re-trace on the device;
+        // its training forward has waited for its status words anyway)
+        const bool can_spec = st->spec_bwd && st->bwd_mode >= 2 && st->est_valid && st->est_hw == (size_t)H * W && st->key_cap > 0 && !st->deterministic;
         if (!ready && !can_spec) { HIPCHK(hipEventSynchronize(st->hit_ev)); ready = true; }
         unsigned n_hits = 0; bool record_ok = true, spec = false;
         st->last_bwd_spec = ready ? 0 : 1;
@@ -1841,6 +1843,9 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
             unsigned long long g = (unsigned long long)st->est_hits + st->est_hits / 8 + (unsigned long long)st->spec_margin;
             n_hits = (unsigned)(g < st->key_cap ? g : st->key_cap); spec = true;
         }
+        if (!record_ok && st->deterministic)
+            LRT_FAIL(LRT_ERR_STATE, "lrt_backward: option deterministic: the forward's hit record overflowed (hit_cap %d%s), so the ordered reduction "
+                     "cannot run and the re-tracing backward would add with float atomics", st->hit_cap, st->hit_cap_auto ? "" : ", hit_cap_auto 0");
         if (record_ok) {
             const int TW = 1 << st->tile_w_log2, TH = 64 / TW;
             tp.tw_log2 = st->tile_w_log2; tp.tiles_x = (W + TW - 1) / TW; tp.tiles_y = (H + TH - 1) / TH;
@@ -1861,8 +1866,17 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
             const bool bucket = bk_nb > 0 && bk_nb <= BK_MAX_NB && ((unsigned long long)H * W) < (1ull << (32 - bk_shift)) && tp.n_tiles > 0 && (spec || n_hits > 0) && 10 + 3 * M + (accum_out ? 1 : 0) <= 64
                                 && (LRT_HAS_LEGACY || st->fast_valid)       // (the product's per-ray preparation reads the colour pass's record: k_bwd_prep2)
                                 && (!rays || st->fast_valid);               // (so does its ray-gradient pass)
+            if (!bucket && st->deterministic && (spec || n_hits > 0)) {
+                // the sums would come from float atomics in arrival order: refuse rather than break the option's promise (bit-reproducible results)
+                const char* why = 10 + 3 * M + (accum_out ? 1 : 0) > 64 ? "the SH table is wider than the ordered reduction's row (10 + 3 M + 1 <= 64 lanes: M <= 17)"
+                                : !st->fast_valid ? "the forward left no colour record (a forward of the packet kernel, fwd_mode 0, or defer_colour 0)"
+                                : !sorted ? "the frame's hits exceed the record buffers (key list)"
+                                : "the image or the scene is too large for the bucketed reduction";
+                LRT_FAIL(LRT_ERR_STATE, "lrt_backward: option deterministic: %s (M = %d); the re-tracing backward would add with float atomics", why, M);
+            }
             if (!bucket) { rc = zero_grads(); if (rc) return rc; }
             if (bucket) {
+                st->last_bwd_path = spec ? 2 : 1;
                 ScopedTimer tm(st, 2, stream);
                 const int hw = H * W;
                 int rpg = hw <= 16 * BK_MAX_NG ? 16 : (hw + BK_MAX_NG - 1) / BK_MAX_NG;
@@ -1933,6 +1947,7 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
                 return LRT_OK;
             }
 #ifdef LRT_LEGACY      // bwd_mode 1 (replay + atomics) and 2 (sorted reduction): the cross-check library only
+            st->last_bwd_path = rays ? 3 : 4;
             if (rays) { tp.guard = 0; tp.n_hits_dev = nullptr; return launch_trace(st, tp, true, stream); }     // (they have no ray gradients: re-trace)
             if (tp.n_tiles > 0 && !sorted) {
                 ScopedTimer tm(st, 2, stream);
@@ -1983,14 +1998,18 @@ static int backward_impl(lrt_state* st, int H, int W, const float* ray_o, const 
 #else
             // no bucketed replay for this call (SH table wider than a wave's row, a forward of the packet kernel, more than 16384 buckets): re-trace.
             // The gradients were cleared above; a speculated record decision is moot (the re-trace is unconditional: guard 0)
-            tp.guard = 0; tp.n_hits_dev = nullptr;
+            tp.guard = 0; tp.n_hits_dev = nullptr; st->last_bwd_path = 3;
             return launch_trace(st, tp, true, stream);
 #endif
         }
         // a ray composited more hits than the record holds: this frame is re-traced (an order of magnitude slower); absorb_status
         // has doubled the capacity for the following ones
     }
+    if (st->deterministic && !(st->hits_valid && st->replay_enabled && st->hit_H == H && st->hit_W == W))
+        LRT_FAIL(LRT_ERR_STATE, "lrt_backward: option deterministic: no hit record of this forward to replay (bwd_mode %d, or another forward / build "
+                 "replaced it); the re-tracing backward would add with float atomics", st->bwd_mode);
     rc = zero_grads(); if (rc) return rc;
+    st->last_bwd_path = 3;
     return launch_trace(st, tp, true, stream);   // no (complete) record: re-trace like the reference
 }
 

@@ -91,7 +91,9 @@ class Tracer(nn.Module):
         order (library option ``deterministic``: a Gaussian's records by ray, the pieces of a run in wave order), the forward keeps no
         learnt state (first-slab widths, carried Morton order, the previous build's box) and the hit weights come from the backward
         (implies deferred_accum: the forward's are float atomics).  Slower (build and forward without their learnt tables, a second pass
-        over the records); a resumed training run then repeats the uninterrupted one bit for bit."""
+        over the records); a resumed training run then repeats the uninterrupted one bit for bit.  Limits: an SH table of at most M = 17
+        coefficients per channel, the default forward / backward modes and a hit record that may grow (hit_cap_auto) -- otherwise the backward
+        raises LrtError rather than fall back to sums in arrival order."""
         super().__init__()
         # the reference creates its OptiX context here (zero-argument ctor, module-level singleton in
         # lib/gaussian_renderer/__init__.py:11); ours is a cheap host object, device state is created lazily

@@ -87,9 +87,10 @@ class HipBackend:
     def build(self, means, scales, rotations, opacities, mod=1.0, cull_rays=None):
         self._C.build_from_gaussians(self.state, means, scales, rotations, opacities, mod, cull_rays=cull_rays)
 
-    def forward(self, ray_o, ray_d, means, scales, rotations, opacities, shs, deg, bg, mod=1.0):
+    def forward(self, ray_o, ray_d, means, scales, rotations, opacities, shs, deg, bg, mod=1.0, training=True):
+        """training=False: no backward follows -- with option deferred_accum the forward keeps its own (exact) weights."""
         e = torch.empty(0, device=means.device)
-        out, _, accum = self._C.trace_surfels(self.state, True, ray_o, ray_d, e, bg, means, shs, deg, e, opacities,
+        out, _, accum = self._C.trace_surfels(self.state, bool(training), ray_o, ray_d, e, bg, means, shs, deg, e, opacities,
                                               scales, mod, rotations, e, e, e, e, False, False)
         self.last_serial = self.state.last_serial      # identifies the hit record this forward left in the library state
         return out, accum
@@ -411,7 +412,12 @@ class ShardedTracer:
         self._cull_prev_key = key if not (isinstance(key, tuple) and len(key) == 4 and key[0] is None) else None
         self.cull_readbacks += 1 if g is None else 0
 
-    def forward(self, ray_o, ray_d, means, scales, rotations, opacities, shs, deg, bg, mod=1.0, rebuild=True, cull_key=None):
+    def forward(self, ray_o, ray_d, means, scales, rotations, opacities, shs, deg, bg, mod=1.0, rebuild=True, cull_key=None, training=None):
+        """training: a backward of this forward follows (default: grad mode is on).  With deferred_accum / deterministic a training forward
+        returns `accum` all-zero and the backward completes it; any other forward (evaluation renders, torch.no_grad()) returns the exact
+        weights at once and its backward, if one is called, does not write them again."""
+        training = torch.is_grad_enabled() if training is None else bool(training)
+        defer = self.deferred_accum and training
         if torch.is_grad_enabled() and (ray_o.requires_grad or ray_d.requires_grad):
             raise ValueError("ShardedTracer: ray gradients (rays that require grad) are not supported under azimuth sharding; "
                              "use diff_lidar_tracer.Tracer")
@@ -451,15 +457,17 @@ class ShardedTracer:
             rs = -1 if cull_key is None else (cull_key if isinstance(cull_key, int) and 0 <= cull_key < 2 ** 30 else (hash(cull_key) & 0x3fffffff))
             if rs != getattr(self, "_ray_set", None):
                 self.backend.state.set_option("ray_set", rs); self._ray_set = rs
-        out_loc, accum_loc = self.backend.forward(self._ro, self._rd, means, scales, rotations, opacities, shs,
-                                                  deg, bg, mod)
+        if self._backend_takes(self.backend.forward, "training"):
+            out_loc, accum_loc = self.backend.forward(self._ro, self._rd, means, scales, rotations, opacities, shs, deg, bg, mod, training=training)
+        else:                                                                     # backend without the flag (test stand-ins): weights at the forward
+            out_loc, accum_loc = self.backend.forward(self._ro, self._rd, means, scales, rotations, opacities, shs, deg, bg, mod)
         self._out_loc, self._accum_loc = out_loc, accum_loc
         if timed and measure:
             evf = torch.cuda.Event(enable_timing=True); evf.record()
         # what backward() needs of THIS forward: an autograd Function keeps it in its ctx (renderer._ShardedTrace), so that a second
         # forward before loss.backward() -- an evaluation render, another frame -- cannot make the backward differentiate the wrong slab
         self.last_ctx = {"slab": (a, b), "ro": self._ro, "rd": self._rd, "out_loc": out_loc, "accum_loc": accum_loc,
-                         "serial": getattr(self.backend, "last_serial", None), "build_id": self._build_id, "mod": mod}
+                         "serial": getattr(self.backend, "last_serial", None), "build_id": self._build_id, "mod": mod, "deferred": defer}
         if self.world == 1 and not self.force_collectives:
             return out_loc, accum_loc
         # all_gather needs equal shapes: slabs padded to the widest one; element 0 of the message = this rank's status word
@@ -537,7 +545,7 @@ class ShardedTracer:
             self._flat_dirty = True                                        # until this step has left its lists behind
         if self._backend_takes(self.backend.backward, "grads_out"):
             kw = {"forward_serial": fc.get("serial")} if self._backend_takes(self.backend.backward, "forward_serial") else {}
-            if self.deferred_accum:
+            if fc.get("deferred", self.deferred_accum):
                 # the backward completes the weights: into the forward's own (all-zero) tensor, or -- with an exchange to follow -- straight into
                 # the flat buffer's accum view (no 4 P-byte copy; under the prezero protocol that view is all-zero on entry like the rest)
                 kw["accum_out"] = lay.views["accum"] if exchanging else accum_loc_
@@ -559,8 +567,8 @@ class ShardedTracer:
                 self._xchg_pack(lay, msg, cap, accum_loc_, with_rows=False)
                 self._prev_lists, self._flat_dirty = (msg, 1, cap, words), False
             return {**lay.views, "accum": accum_loc_}          # nothing to exchange: the forward's own accum tensor, no 4 P-byte copy
-        if not self.deferred_accum:
-            lay.views["accum"].copy_(accum_loc_)
+        if not fc.get("deferred", self.deferred_accum):
+            lay.views["accum"].copy_(accum_loc_)                # the forward's own weights (no deferral, or a forward without a backward)
         if reduce and (self.world > 1 or self.force_collectives):
             with self._Region(self, "gradient_exchange", lay.flat.device):
                 mode = self.exchange

@@ -120,7 +120,8 @@ def main(argv=None) -> int:
                     "the backward (renderer.deferred_accum, the default here: the loop reads them after the backward only)")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (Tracer(deterministic=True): the backward adds a Gaussian's records up by ray and "
                     "the pieces of long runs in order, the forward keeps no learnt tables): ~1.4 x the tracer time; a run resumed from a checkpoint then equals the "
-                    "uninterrupted one bit for bit (with lambda_cd = 0: the Chamfer backward adds with float atomics)")
+                    "uninterrupted one bit for bit (with lambda_cd = 0: the Chamfer backward adds with float atomics).  SH tables of at most 17 coefficients per "
+                    "channel (sh_degree <= 3 with a table sized for it): the backward raises otherwise")
     ap.add_argument("--refine-poses", action="store_true", help="also learn a per-frame se(3) correction of the recorded sensor poses through the tracer's "
                     "ray gradients (lidar_rt_amd.poses); written as poses<it>.pth beside each checkpoint and read back by --resume")
     ap.add_argument("--pose-lr-trans", type=float, default=1e-3, help="--refine-poses: Adam learning rate of the translation part (m)")

@@ -168,3 +168,74 @@ def test_deferred_weights_on_s200k_and_through_the_renderer():
         renderer.deferred_accum, renderer.tracer_2dgs = old
     assert got[False][0].any() and not got[True][0].any()
     assert rel_l2(got[True][1], got[False][1]) < 2e-6
+
+
+@pytest.mark.parametrize("kind", ["deferred_accum", "deterministic"])
+def test_sharded_forward_without_a_backward_gives_exact_weights(s10k, kind):
+    """ShardedTracer(deferred_accum / deterministic): a forward that no backward follows (grad mode off) keeps the forward's weights -- the
+    oracle's, and those of a tracer without the option; a training forward still leaves them zero and its backward fills them."""
+    from lidar_rt_amd.parallel import ShardedTracer
+    sc, o, d, dL = s10k
+    fw, _ = _oracle(sc, o, d, 3, scenes.BG_DEFAULT, dL)
+    t = {k: torch.as_tensor(np.asarray(v, np.float32), device=DEV) for k, v in sc.items()}
+    ro, rd, up = torch.as_tensor(o, device=DEV), torch.as_tensor(d, device=DEV), torch.as_tensor(dL, device=DEV)
+    args = (t["means"], t["scales"], t["rotations"], t["opacities"], t["shs"], 3, torch.as_tensor(scenes.BG_DEFAULT, device=DEV))
+    out_p, acc_p = ShardedTracer().forward(ro, rd, *args)
+    tr = ShardedTracer(**{kind: True})
+    with torch.no_grad():
+        out, acc = tr.forward(ro, rd, *args)
+    torch.cuda.synchronize()
+    acc, acc_p = acc.cpu().numpy(), acc_p.cpu().numpy()
+    assert frac_outside(acc, fw["accum"], 1e-4) <= 1e-3 and rel_l2(acc, fw["accum"]) < 1e-5, kind
+    assert rel_l2(acc, acc_p) < 2e-6, kind
+    np.testing.assert_array_equal(acc > 0, acc_p > 0)
+    np.testing.assert_array_equal(out.cpu().numpy(), out_p.cpu().numpy())
+    # the training step keeps deferring: zero after the forward, the same weights after the backward
+    _, acc_t = tr.forward(ro, rd, *args)
+    torch.cuda.synchronize()
+    assert not acc_t.cpu().numpy().any(), kind
+    g = tr.backward(*args, up)
+    torch.cuda.synchronize()
+    assert rel_l2(g["accum"].cpu().numpy(), acc_p) < 2e-6, kind
+    np.testing.assert_array_equal(g["accum"].cpu().numpy() > 0, acc_p > 0)
+
+
+@pytest.mark.parametrize("kind", ["deferred_accum", "deterministic"])
+def test_sharded_renderer_without_grad_gives_exact_weights(s10k, kind):
+    """renderer.raytracing through renderer.sharded = ShardedTracer(deferred_accum / deterministic) under torch.no_grad(): the weights equal
+    the single-GPU renderer's at once; with grad mode on they come from loss.backward() and equal them too."""
+    import types
+    from lidar_rt_amd import renderer
+    from lidar_rt_amd.parallel import ShardedTracer
+    from tests.test_renderer_gpu import Asset
+    sc, o, d, _ = s10k
+    asset = Asset(sc, slice(None))
+    args = types.SimpleNamespace(dynamic=False, opt=types.SimpleNamespace(use_rayhit=False), pipe=types.SimpleNamespace())
+    sensor = (torch.as_tensor(o, device=DEV), torch.as_tensor(d, device=DEV), torch.zeros(3, device=DEV))
+    bg = torch.tensor(scenes.BG_DEFAULT)
+    old = renderer.deferred_accum, renderer.deterministic, renderer.tracer_2dgs, renderer.sharded
+    try:
+        renderer.deferred_accum, renderer.deterministic, renderer.tracer_2dgs, renderer.sharded = False, False, None, None
+        with torch.no_grad():
+            single = renderer.raytracing(0, [asset], sensor, bg, args)["accum_gaussian_weight"].cpu().numpy()
+        renderer.sharded = ShardedTracer(**{kind: True})
+        with torch.no_grad():
+            pkg = renderer.raytracing(0, [asset], sensor, bg, args)
+        torch.cuda.synchronize()
+        got = pkg["accum_gaussian_weight"].cpu().numpy()
+        assert single.any()
+        assert rel_l2(got, single) < 2e-6, kind
+        np.testing.assert_array_equal(got > 0, single > 0)
+        # training render: zero until the backward, complete after it
+        for p in asset.params():
+            p.grad = None
+        pkg = renderer.raytracing(0, [asset], sensor, bg, args)
+        before = pkg["accum_gaussian_weight"].detach().cpu().numpy()
+        (pkg["depth"].sum() + pkg["intensity"].sum()).backward()
+        torch.cuda.synchronize()
+        after = pkg["accum_gaussian_weight"].detach().cpu().numpy()
+        assert not before.any(), kind
+        assert rel_l2(after, single) < 2e-6, kind
+        np.testing.assert_array_equal(after > 0, single > 0)
+    finally:
+        renderer.deferred_accum, renderer.deterministic, renderer.tracer_2dgs, renderer.sharded = old

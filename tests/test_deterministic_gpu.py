@@ -97,3 +97,98 @@ def test_switching_the_option_off_restores_the_learnt_tables():
     assert tr.deferred_accum and st.get_option("deterministic", DEV) == 1 and st.get_option("carry_order", DEV) == 0
     st.set_option("deterministic", 0)
     assert st.get_option("deterministic", DEV) == 0 and st.get_option("carry_order", DEV) == 1
+
+
+# ---- the option holds or says no: the cases where the ordered (bucketed) reduction cannot run ------------------------------------------
+# library readout `last_bwd_path`: 1 = bucketed reduction decided on the host, 2 = bucketed with the re-trace behind it decided on the device
+# (speculated record size), 3 = re-tracing backward (float atomics), 4 = the cross-check library's replay / sorted reductions
+BUCKETED, RETRACE = 1, 3
+
+
+def _case(which):
+    """(scene, rays, options) of a case in which the bucketed reduction may not be available."""
+    if which == "dense-translucent":
+        sc, o, d = scenes.dense_translucent()
+        return {k: np.asarray(v, np.float32) for k, v in sc.items()}, o, d, {}
+    sc, o, d = _scene_with_a_wall("s10k")
+    if which == "sh-width-25":
+        extra = np.random.default_rng(3).normal(0, 0.02, (sc["shs"].shape[0], 9, 3)).astype(np.float32)
+        sc["shs"] = np.ascontiguousarray(np.concatenate([sc["shs"], extra], axis=1))
+        return sc, o, d, {}
+    return sc, o, d, {"fwd-mode-0": {"fwd_mode": 0}, "hit-cap-8": {"hit_cap": 8, "hit_cap_auto": 0}}[which]
+
+
+def _sharded(opts):
+    tr = ShardedTracer(deterministic=True)
+    for k, v in opts.items():
+        tr.backend.state.set_option(k, v)
+    return tr
+
+
+def _ray_step(tr, t, o, d, dL, n=1):
+    from tests.hip_util import settings
+    for _ in range(n):
+        ro = o.clone().requires_grad_(True); rd = d.clone().requires_grad_(True)
+        tt = {k: v.clone().requires_grad_(True) for k, v in t.items()}
+        tr.build_from_gaussians(tt["means"], tt["scales"], tt["rotations"], tt["opacities"])
+        out, acc = tr(ro, rd, None, tt["means"], torch.zeros_like(tt["means"]), shs=tt["shs"], opacities=tt["opacities"], scales=tt["scales"],
+                      rotations=tt["rotations"], tracer_settings=settings(scenes.BG_DEFAULT, 3))
+        out.backward(dL)
+    torch.cuda.synchronize()
+    return out.detach().clone(), {**{k: tt[k].grad.clone() for k in KEYS if k != "accum"}, "accum": acc.detach().clone(), "ray_o": ro.grad.clone(),
+                                  "ray_d": rd.grad.clone()}
+
+
+@pytest.mark.parametrize("which", ["sh-width-25", "fwd-mode-0", "hit-cap-8", "dense-translucent", "ray-grads"])
+def test_deterministic_holds_or_refuses(which):
+    """Each case gives the same bits from a fresh state and from a state with another history -- having run the ordered reduction -- or its
+    backward raises an error that names the option.  A silent fallback to the float-atomic re-trace fails."""
+    from lidar_rt_amd import _capi
+    from lidar_rt_amd.diff_lidar_tracer import Tracer
+    sc, o, d, opts = (*_scene_with_a_wall("s10k"), {}) if which == "ray-grads" else _case(which)
+    H, W = o.shape[:2]
+    t = {k: torch.as_tensor(v, device=DEV) for k, v in sc.items()}
+    ro, rd = torch.as_tensor(np.asarray(o, np.float32), device=DEV), torch.as_tensor(np.asarray(d, np.float32), device=DEV)
+    dL = torch.as_tensor(scenes.upstream_grad(H, W), device=DEV)
+    t2 = dict(t); t2["means"] = t["means"] + 0.01
+    ro2 = (ro + torch.tensor([0.3, -0.2, 0.05], device=DEV)).contiguous()
+    if which == "ray-grads":
+        make, step, state = (lambda: Tracer(deterministic=True)), _ray_step, (lambda tr: tr.optix_context)
+    else:
+        make, step, state = (lambda: _sharded(opts)), _step, (lambda tr: tr.backend.state)
+    try:
+        a = make(); out_a, g_a = step(a, t, ro, rd, dL)
+    except _capi.LrtError as ex:
+        assert "deterministic" in str(ex), str(ex)
+        return
+    assert state(a).get_option("last_bwd_path", DEV) == BUCKETED, which         # it held: the ordered reduction ran
+    out_b, g_b = step(make(), t, ro, rd, dL)
+    c = make()
+    step(c, t2, ro2, rd, dL, n=2)
+    out_c, g_c = step(c, t, ro, rd, dL)
+    assert state(c).get_option("last_bwd_path", DEV) == BUCKETED, which
+    for name, (out_x, g_x) in (("fresh", (out_b, g_b)), ("another history", (out_c, g_c))):
+        assert torch.equal(out_a, out_x), (which, name)
+        for k in g_a:
+            assert torch.equal(g_a[k], g_x[k]), (which, name, k, int((g_a[k] != g_x[k]).sum()))
+
+
+@pytest.mark.parametrize("M", [16, 17])
+def test_deterministic_runs_the_ordered_reduction(M):
+    """The supported cases say which path ran: the bucketed (ordered) reduction, decided on the host; the option off and bwd_mode 0: the
+    re-trace."""
+    sc, o, d = scenes.s10k()
+    sc = dict(sc)
+    if M > 16:
+        sc["shs"] = np.ascontiguousarray(np.concatenate([sc["shs"], np.zeros((sc["shs"].shape[0], M - 16, 3), np.float32)], 1))
+    t = {k: torch.as_tensor(np.asarray(v, np.float32), device=DEV) for k, v in sc.items()}
+    ro, rd = torch.as_tensor(o, device=DEV), torch.as_tensor(d, device=DEV)
+    dL = torch.as_tensor(scenes.upstream_grad(*o.shape[:2]), device=DEV)
+    tr = ShardedTracer(deterministic=True)
+    for _ in range(2):                                    # a second step: nothing speculated either
+        _step(tr, t, ro, rd, dL)
+        assert tr.backend.state.get_option("last_bwd_path", DEV) == BUCKETED
+    plain = ShardedTracer()
+    plain.backend.state.set_option("bwd_mode", 0)
+    _step(plain, t, ro, rd, dL)
+    assert plain.backend.state.get_option("last_bwd_path", DEV) == RETRACE

@@ -91,3 +91,33 @@ def test_sensor_inside_the_geometry_matches_the_oracle(mode):
     if mode.get("fwd_mode") == 2 or mode.get("bwd_mode") == 0:     # replay backward of the recorded (near-ray) hits / re-tracing backward with its own near-ray replay
         for k in ("means", "opacities", "shs"):
             assert rel_l2(h["grads"][k].reshape(bw[k].shape), bw[k]) < 2e-3, k        # measured < 5e-5 in every mode (tests/tools/near_dbg.py)
+
+
+@pytest.mark.parametrize("mode", [MODES[i] for i in _SEL_B], ids=[IDS[i] for i in _SEL_B])
+def test_no_hit_is_lost_at_a_slab_border(mode):
+    """Near rays whose second quad lies on a border of the lazy depth slabs (1.5 / 6 / 24 / 96 / 384 m), at depths where a box that fitted
+    its quad exactly would straddle the border (tests/test_near_slab_borders.py).  Every ray is a near ray; every ray, every channel
+    matches the oracle fed in ascending t -- no fraction of rays is allowed to differ.  (Tolerance 1e-3: the float32 hit point of a quad 24-384 m
+    away differs from the oracle's by ~1e-5 m, a few 1e-5 of the Gaussian's weight; a lost hit changes a ray's alpha by ~0.5.)"""
+    from tests.test_near_slab_borders import straddling_scene
+    sc, o, d = straddling_scene()
+    H, W = o.shape[:2]
+    dL = scenes.upstream_grad(H, W, seed=6)
+    oracle.set_sorted_anyhit(True)
+    try:
+        fw, bw = oracle_run(sc, o, d, 0, scenes.BG_DEFAULT, dL)
+    finally:
+        oracle.set_sorted_anyhit(False)
+    from oracle.bruteforce import QuadScene
+    qs = QuadScene(sc["means"], sc["scales"], sc["rotations"], sc["opacities"])
+    assert all(bool((qs.candidates(oo, dd)[1] < 0.2).any()) for oo, dd in zip(o.reshape(-1, 3), d.reshape(-1, 3)))
+    assert (fw["n_comp"] >= 1).all() and fw["accum"][:H * W].min() > 0          # every border quad is composited by the oracle
+    h = run_hip(sc, o, d, 0, scenes.BG_DEFAULT, dL, opts=mode)
+    np.testing.assert_allclose(h["out"], fw["out"], rtol=1e-3, atol=1e-4)
+    np.testing.assert_allclose(h["accum"], fw["accum"], rtol=1e-3, atol=1e-6)
+    assert (h["accum"][:H * W] > 0).all()                                      # every border quad composited
+    if mode.get("fwd_mode") == 2 or mode.get("bwd_mode") == 0:
+        for k in ("opacities", "shs"):                                          # a lost hit zeroes its Gaussian's rows
+            assert rel_l2(h["grads"][k].reshape(bw[k].shape), bw[k]) < 2e-3, k
+        # d/dmean of a quad 24-384 m away goes through the float32 hit point (measured 2.6e-3 in every mode)
+        assert rel_l2(h["grads"]["means"].reshape(bw["means"].shape), bw["means"]) < 5e-3
