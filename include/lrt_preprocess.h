@@ -14,7 +14,8 @@
  *
  * Assets are contiguous segments of the parameter arrays: seg_start (A+1 int32, device) and poses (A x 8 float32,
  * device): [tx, ty, tz, qw, qx, qy, qz, posed] with posed = 0 for an asset without a rigid pose (background).
- * Poses are constants (the reference keeps them without gradient, lib/scene/bounding_box.py:53,72).
+ * The reference keeps poses without gradient (lib/scene/bounding_box.py:53,72); lrt_preprocess_backward_poses also returns the
+ * gradient of the pose table, for refining the actors' tracking boxes.
  *
  * Conventions: as in lrt.h -- device pointers to contiguous float32, stream-ordered on `device`, 0 or a negative code
  * with lrt_last_error().
@@ -22,6 +23,7 @@
 #ifndef LRT_PREPROCESS_H_INCLUDED
 #define LRT_PREPROCESS_H_INCLUDED
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -40,6 +42,20 @@ int lrt_preprocess_backward(int device, int P, int A, const int32_t* seg_start, 
                             const float* scales, const float* opacities, const float* d_means, const float* d_scales,
                             const float* d_rotations, const float* d_opacities, float* d_xyz, float* d_log_scales,
                             float* d_rot_raw, float* d_opacity_logit, void* stream);
+
+/* Bytes of the workspace lrt_preprocess_backward_poses needs for P Gaussians in A assets (16 floats per (workgroup, asset) row). */
+size_t lrt_preprocess_pose_work_bytes(int P, int A);
+
+/* lrt_preprocess_backward, plus the gradient of the pose table: d_poses (A x 8, overwritten) =
+ * [dL/dtx, dL/dty, dL/dtz, dL/dqw, dL/dqx, dL/dqy, dL/dqz, 0] of each posed asset -- the quaternion as stored: through R(q/|q|) of the
+ * means and through the composition q (x) normalize(raw) of the rotations.  Rows of unposed or empty assets and column 7 are zero.
+ * `xyz` is the forward's local (P,3) input; `work` a device buffer of at least lrt_preprocess_pose_work_bytes(P, A) bytes, used
+ * within the call's stream order only.  No atomics: the result is the same bits on every call. */
+int lrt_preprocess_backward_poses(int device, int P, int A, const int32_t* seg_start, const float* poses, const float* rot_raw,
+                                  const float* scales, const float* opacities, const float* d_means, const float* d_scales,
+                                  const float* d_rotations, const float* d_opacities, float* d_xyz, float* d_log_scales,
+                                  float* d_rot_raw, float* d_opacity_logit, const float* xyz, float* d_poses, void* work,
+                                  size_t work_bytes, void* stream);
 
 #ifdef __cplusplus
 }

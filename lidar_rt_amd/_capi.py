@@ -21,7 +21,7 @@ EXPORTS = ("lrt_abi_version", "lrt_last_error", "lrt_create", "lrt_destroy", "lr
            # include/lrt_knn.h
            "lrt_knn_mean_dist2",
            # include/lrt_preprocess.h
-           "lrt_preprocess_forward", "lrt_preprocess_backward")
+           "lrt_preprocess_forward", "lrt_preprocess_backward", "lrt_preprocess_pose_work_bytes", "lrt_preprocess_backward_poses")
 
 ABI_VERSION = 5          # LRT_ABI_VERSION of include/lrt.h this binding was written against
 
@@ -91,6 +91,9 @@ def load():
     lib.lrt_knn_mean_dist2.restype = ci; lib.lrt_knn_mean_dist2.argtypes = [vp, ci, vp, vp, vp]
     lib.lrt_preprocess_forward.restype = ci; lib.lrt_preprocess_forward.argtypes = [ci, ci, ci] + [vp] * 11
     lib.lrt_preprocess_backward.restype = ci; lib.lrt_preprocess_backward.argtypes = [ci, ci, ci] + [vp] * 14
+    lib.lrt_preprocess_pose_work_bytes.restype = C.c_size_t; lib.lrt_preprocess_pose_work_bytes.argtypes = [ci, ci]
+    lib.lrt_preprocess_backward_poses.restype = ci
+    lib.lrt_preprocess_backward_poses.argtypes = [ci, ci, ci] + [vp] * 16 + [C.c_size_t, vp]
     if lib.lrt_abi_version() != ABI_VERSION:
         raise LrtError("liblrt_hip.so ABI version mismatch; rebuild with `python -m lidar_rt_amd.build --force`")
     if os.environ.get("LRT_TRACE_CALLS"):                    # developer aid: name every entry point on stderr and wait for the device after it

@@ -29,6 +29,12 @@ def run(args) -> dict:
     scene.training_setup(opt)
     model_params, iteration = torch.load(args.ckpt, map_location=dev, weights_only=False)
     scene.restore(model_params, opt)
+    if args.boxes:
+        # the actors' refined tracking boxes (python -m lidar_rt_amd.train --refine-boxes writes them); test frames interpolate the corrections
+        from .actor_poses import ActorPoses
+        if not seq.boxes:
+            raise SystemExit(f"--boxes: {args.data} has no tracking boxes (boxes.npz)")
+        ActorPoses.from_state_dict(seq.boxes, torch.load(args.boxes, map_location=dev, weights_only=False)).install(scene.gaussians_assets)
     frames = {"test": seq.test_frames or seq.train_frames, "train": seq.train_frames, "all": sorted(set(seq.train_frames) | set(seq.test_frames))}[args.frames]
     if args.max_frames > 0:
         frames = frames[:args.max_frames]
@@ -51,6 +57,7 @@ def main(argv=None) -> int:
     ap.add_argument("--max-points", type=int, default=2_000_000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--boxes", default=None, help="refined actor boxes (boxes<it>.pth of python -m lidar_rt_amd.train --refine-boxes) to render with")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     args = ap.parse_args(argv)
     res = run(args)

@@ -8,7 +8,9 @@ the reference's chain of PyTorch kernels in front of every trace
   concatenated in asset order (``torch.cat`` of leaves is differentiable; gradients flow back to each asset).
 * ``seg_start`` (A+1,) int32 device tensor: asset a owns Gaussians ``[seg_start[a], seg_start[a+1])``.
 * ``poses`` (A,8) float32 device tensor ``[tx,ty,tz, qw,qx,qy,qz, posed]``; ``posed = 0`` for the background / static assets.
-  Poses carry no gradient (the reference's do not either, lib/scene/bounding_box.py:53,72).
+  The reference keeps poses without gradient (lib/scene/bounding_box.py:53,72); here a ``poses`` table that requires grad receives
+  dL/dposes (A,8) from ``lrt_preprocess_backward_poses`` (zero rows for unposed / empty assets, column 7 zero): per-frame box refinement,
+  ``lidar_rt_amd.actor_poses``.  Without it the backward is the plain launch.
 
 HIP tensors only; there is no CPU path (the CPU restatement used by the tests lives outside this package).
 """
@@ -51,12 +53,13 @@ class _FusedActivations(torch.autograd.Function):
             _capi.check(_capi.load().lrt_preprocess_forward(idx, P, A, p(seg_start), p(poses), p(xyz), p(log_scales), p(rot_raw),
                                                             p(opacity_logit), p(means), p(scales), p(rots), p(opac), stream),
                         "lrt_preprocess_forward")
-        ctx.save_for_backward(rot_raw, scales, opac, seg_start, poses)
+        ctx.pose_grad = bool(ctx.needs_input_grad[5])
+        ctx.save_for_backward(rot_raw, scales, opac, seg_start, poses, xyz if ctx.pose_grad else None)
         return means, scales, rots, opac
 
     @staticmethod
     def backward(ctx, d_means, d_scales, d_rots, d_opac):
-        rot_raw, scales, opac, seg_start, poses = ctx.saved_tensors
+        rot_raw, scales, opac, seg_start, poses, xyz = ctx.saved_tensors
         P, A = rot_raw.shape[0], poses.shape[0]
         dev = rot_raw.device
         z = lambda g, like: (torch.zeros_like(like) if g is None else g.contiguous().to(torch.float32))
@@ -68,10 +71,19 @@ class _FusedActivations(torch.autograd.Function):
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
         with torch.cuda.device(idx):
-            _capi.check(_capi.load().lrt_preprocess_backward(idx, P, A, p(seg_start), p(poses), p(rot_raw), p(scales), p(opac),
-                                                             p(d_means), p(d_scales), p(d_rots), p(d_opac), p(d_xyz), p(d_ls),
-                                                             p(d_rot), p(d_lo), stream), "lrt_preprocess_backward")
-        return d_xyz, d_ls, d_rot, d_lo, None, None
+            if not ctx.pose_grad:
+                _capi.check(_capi.load().lrt_preprocess_backward(idx, P, A, p(seg_start), p(poses), p(rot_raw), p(scales), p(opac),
+                                                                 p(d_means), p(d_scales), p(d_rots), p(d_opac), p(d_xyz), p(d_ls),
+                                                                 p(d_rot), p(d_lo), stream), "lrt_preprocess_backward")
+                return d_xyz, d_ls, d_rot, d_lo, None, None
+            lib = _capi.load()
+            nb = int(lib.lrt_preprocess_pose_work_bytes(P, A))
+            work = torch.empty((nb + 3) // 4, dtype=torch.float32, device=dev)       # stream-ordered caching allocator: no host wait
+            d_poses = torch.empty(A, 8, dtype=torch.float32, device=dev)
+            _capi.check(lib.lrt_preprocess_backward_poses(idx, P, A, p(seg_start), p(poses), p(rot_raw), p(scales), p(opac), p(d_means),
+                                                          p(d_scales), p(d_rots), p(d_opac), p(d_xyz), p(d_ls), p(d_rot), p(d_lo), p(xyz),
+                                                          p(d_poses), p(work), nb, stream), "lrt_preprocess_backward_poses")
+        return d_xyz, d_ls, d_rot, d_lo, None, d_poses
 
 
 def fused_activations(xyz, log_scales, rot_raw, opacity_logit, seg_start, poses):

@@ -68,6 +68,15 @@ def run(args) -> dict:
         # one se(3) correction per training frame, learnt through the tracer's ray gradients (lidar_rt_amd.poses); saved beside each checkpoint
         from .poses import SensorPoses
         sensor_poses = SensorPoses(seq.frames, seq.train_frames, lr_trans=args.pose_lr_trans, lr_rot=args.pose_lr_rot)
+    box_poses = None
+    if args.refine_boxes:
+        # one se(3) correction per (actor, training frame) with a box, learnt through the pose-table gradient of the fused pre-processing
+        # (lidar_rt_amd.actor_poses); saved beside each checkpoint.  Identical on every rank: so are the gradients it comes from
+        if not seq.boxes:
+            raise SystemExit(f"--refine-boxes: {args.data} has no tracking boxes (boxes.npz)")
+        from .actor_poses import ActorPoses
+        box_poses = ActorPoses(seq.boxes, seq.train_frames, lr_trans=args.box_lr_trans, lr_rot=args.box_lr_rot)
+        box_poses.install(scene.gaussians_assets)
     if args.resume:
         model_params, it0 = torch.load(args.resume, map_location=dev, weights_only=False)
         scene.restore(model_params, opt)
@@ -75,6 +84,9 @@ def run(args) -> dict:
         pp = os.path.join(os.path.dirname(os.path.abspath(args.resume)), f"poses{int(it0)}.pth")
         if sensor_poses is not None and os.path.exists(pp):
             sensor_poses.load_state_dict(torch.load(pp, map_location=dev, weights_only=False))
+        bp = os.path.join(os.path.dirname(os.path.abspath(args.resume)), f"boxes{int(it0)}.pth")
+        if box_poses is not None and os.path.exists(bp):
+            box_poses.load_state_dict(torch.load(bp, map_location=dev, weights_only=False))
     os.makedirs(args.out, exist_ok=True)
     bg = torch.tensor([0.0, 0.0, 1.0], device=dev)       # the reference's background for (intensity, ray-hit, ray-drop): train.py:106
     log, t0 = [], time.perf_counter()
@@ -82,7 +94,8 @@ def run(args) -> dict:
     for it in range(first, args.iters + 1):
         torch.manual_seed(args.seed * 1_000_003 + it)      # the densification's random draws: a function of (seed, iteration) on every rank
         frame = frame_of(args.seed, it, seq.train_frames)
-        res = training.training_step(scene, seq.frames, frame, it, opt, bg, dynamic=bool(seq.meta.get("dynamic")), poses=sensor_poses)
+        res = training.training_step(scene, seq.frames, frame, it, opt, bg, dynamic=bool(seq.meta.get("dynamic")), poses=sensor_poses,
+                                      box_poses=box_poses)
         if it % args.log_every == 0 or it == args.iters:
             row = {"iteration": it, "frame": int(frame), "loss": float(res["loss"]), "depth": float(res["depth"]), "intensity": float(res["intensity"]),
                    "raydrop": float(res["raydrop"]), "points": int(res["points"]), "seconds": round(time.perf_counter() - t0, 3)}
@@ -93,6 +106,8 @@ def run(args) -> dict:
             scene.save(it, os.path.join(args.out, f"chkpnt{it}.pth"))
             if sensor_poses is not None:
                 torch.save(sensor_poses.state_dict(), os.path.join(args.out, f"poses{it}.pth"))
+            if box_poses is not None:
+                torch.save(box_poses.state_dict(), os.path.join(args.out, f"boxes{it}.pth"))
     if renderer.sharded is not None:
         renderer.sharded.check(wait=True)
     elif renderer.tracer_2dgs is not None:
@@ -101,7 +116,7 @@ def run(args) -> dict:
     if world > 1:
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()
-    return {"log": log, "scene": scene, "sequence": seq, "last": res, "poses": sensor_poses}
+    return {"log": log, "scene": scene, "sequence": seq, "last": res, "poses": sensor_poses, "boxes": box_poses}
 
 
 def main(argv=None) -> int:
@@ -126,7 +141,14 @@ def main(argv=None) -> int:
                     "ray gradients (lidar_rt_amd.poses); written as poses<it>.pth beside each checkpoint and read back by --resume")
     ap.add_argument("--pose-lr-trans", type=float, default=1e-3, help="--refine-poses: Adam learning rate of the translation part (m)")
     ap.add_argument("--pose-lr-rot", type=float, default=1e-4, help="--refine-poses: Adam learning rate of the rotation part (rad)")
+    ap.add_argument("--refine-boxes", action="store_true", help="also learn a per-frame se(3) correction of every actor's tracking box through the "
+                    "pose-table gradient of the fused pre-processing (lidar_rt_amd.actor_poses); written as boxes<it>.pth beside each checkpoint and "
+                    "read back by --resume; works with --gpus N")
+    ap.add_argument("--box-lr-trans", type=float, default=1e-3, help="--refine-boxes: Adam learning rate of the translation part (m)")
+    ap.add_argument("--box-lr-rot", type=float, default=1e-4, help="--refine-boxes: Adam learning rate of the rotation part (rad)")
     args = ap.parse_args(argv)
+    if args.refine_boxes and not os.path.exists(os.path.join(args.data, "boxes.npz")):
+        ap.error(f"--refine-boxes: {args.data} has no tracking boxes (boxes.npz)")
     if args.refine_poses and args.gpus > 1:
         ap.error("--refine-poses needs ray gradients, which azimuth sharding (--gpus > 1) does not provide")
     if args.exact_accum and args.deterministic:

@@ -451,10 +451,12 @@ def ssim(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11) -> torch
 
 
 def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: int, opt, background: torch.Tensor,
-                  dynamic: bool = False, chamfer_points_detached: bool = True, poses=None) -> Dict[str, torch.Tensor]:
+                  dynamic: bool = False, chamfer_points_detached: bool = True, poses=None, box_poses=None) -> Dict[str, torch.Tensor]:
     """One iteration of train.py:125-220: render, depth L1 + intensity L1/L2/DSSIM + ray-drop BCE + Chamfer + box
     regularisation, backward, then ``scene.optimize`` with ``means3D.grad`` and the accumulated hit weights.
     ``poses`` (a ``poses.SensorPoses`` over ``frames``): render through its corrected poses and take its optimiser step after the backward.
+    ``box_poses`` (an ``actor_poses.ActorPoses`` installed on the scene's actors): the same for the actors' tracking boxes; on several ranks
+    its corrections are verified identical after every step.
     ``chamfer_points_detached``: the reference builds both point clouds from numpy (lidar_sensor.py:182-183), so its
     Chamfer term carries no gradient; False keeps the predicted points differentiable."""
     from .renderer import raytracing
@@ -469,6 +471,8 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
     sensor = frames if poses is None else poses
     if poses is not None:
         poses.zero_grad()
+    if box_poses is not None:
+        box_poses.zero_grad()
 
     def attempt():
         """render -> losses -> backward (train.py:148-214); everything the optimizer step reads afterwards"""
@@ -513,6 +517,8 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
             for g_ in scene.gaussians_assets:
                 for p_ in g_._params().values():
                     p_.grad = None
+            if box_poses is not None:
+                box_poses.zero_grad()
             pkg, loss, loss_depth, loss_int, loss_drop, loss_cd = attempt()
             redone = 1
             bad = _rnd.sharded.verify_step()
@@ -527,6 +533,10 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
         info = scene.optimize(opt, iteration, pkg["means3D"].grad, pkg["accum_gaussian_weight"])
     if poses is not None:
         poses.step()
+    if box_poses is not None:
+        box_poses.step()
+        if _rnd.sharded is not None:
+            box_poses.check_replicas(_rnd.sharded.group)
     with torch.no_grad():
         # multi-GPU: the replicas are never synchronised (identical gradients + identical seeds keep them identical); verify it now and then
         k_chk = int(getattr(opt, "replica_check_interval", 500))
