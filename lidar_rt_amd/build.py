@@ -8,6 +8,10 @@
 * ``diff_lidar_tracer/_C_ext.*.so`` -- the PyTorch-ROCm C++ extension (pybind11, ``csrc/lrt_torch_ext.cpp``): the reference's
   ``_C`` module surface with at::Tensor arguments on top of the C ABI.  Host code only; it links liblrt_hip.so.
 
+* ``csrc/liblrt_loss.so`` -- the fused range-image training loss (``csrc/lrt_loss.hip``, C ABI ``include/lrt_loss.h``): a second product
+  library with its own source list, content hash and stamp, so that the tracer library's ``source_hash()`` (which keys committed profiles)
+  does not move with it.  Loaded by ``lidar_rt_amd.losses``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -41,6 +45,11 @@ CODEGEN_FLAGS = ["-O3", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
 STAMP = os.path.join(CSRC, "liblrt_hip.srchash")       # the hash of the sources the in-tree library was compiled from (travels with it; git-ignored)
 LIB_LEGACY = os.path.join(CSRC, "liblrt_hip_legacy.so")
 STAMP_LEGACY = os.path.join(CSRC, "liblrt_hip_legacy.srchash")
+# the loss library: same arch and code-generation flags, its own sources (lrt_device_guard.h is shared, read-only)
+LOSS_LIB = os.path.join(CSRC, "liblrt_loss.so")
+LOSS_STAMP = os.path.join(CSRC, "liblrt_loss.srchash")
+LOSS_SOURCES = ["lrt_loss.hip"]
+LOSS_HEADERS = ["lrt_loss_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_loss.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -67,6 +76,46 @@ def source_hash() -> str:
             h.update(f.encode()); h.update(fh.read())
     h.update(" ".join(CODEGEN_FLAGS).encode())            # the same sources under other code-generation flags are another library
     return h.hexdigest()[:16]
+
+
+def loss_source_hash() -> str:
+    """source_hash() of the loss library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(LOSS_SOURCES + LOSS_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def loss_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(LOSS_LIB):
+        return True
+    try:
+        return open(LOSS_STAMP).read().strip() != loss_source_hash()
+    except OSError:
+        return True
+
+
+def build_loss(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_loss.so, compiled when stale; the resource gate runs on it on EVERY call, as on the tracer library."""
+    if force or loss_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", LOSS_LIB] \
+            + [os.path.join(CSRC, s) for s in LOSS_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(LOSS_STAMP, "w") as f:
+            f.write(loss_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(LOSS_LIB)} is up to date (sources {loss_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(LOSS_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return LOSS_LIB
 
 
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
@@ -164,6 +213,7 @@ def _build_product(force: bool, verbose: bool) -> str:
         print(resources.table_md(res, r"^k_fwd_cr4<"), flush=True)
         print(f"{sum(1 for n in res if resources.is_own_kernel(n))} kernels of this project in {os.path.basename(lib)}, none spills", flush=True)
     build_ext(force, verbose)
+    build_loss(force, verbose)
     return lib
 
 

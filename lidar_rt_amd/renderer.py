@@ -99,7 +99,7 @@ def _fused_inputs(frame, assets, dynamic, decomp):
 
 
 def raytracing(frame, gaussian_assets, sensor, background, args, scaling_modifier=1.0, override_color=None,
-               decomp=False):
+               decomp=False, return_rendered=False):
     global tracer_2dgs
     if sharded is None:
         if tracer_2dgs is None or tracer_2dgs.deferred_accum != (bool(deferred_accum) or bool(deterministic)) or tracer_2dgs.deterministic != bool(deterministic):
@@ -180,5 +180,8 @@ def raytracing(frame, gaussian_assets, sensor, background, args, scaling_modifie
         raydrop_prob = prob[..., 1:2]
     else:
         raydrop_prob = torch.sigmoid(raydrop_logits)
-    return {"depth": depth, "intensity": intensities, "raydrop": raydrop_prob, "means3D": means3D,
-            "accum_gaussian_weight": accum.unsqueeze(-1)}
+    pkg = {"depth": depth, "intensity": intensities, "raydrop": raydrop_prob, "means3D": means3D,
+           "accum_gaussian_weight": accum.unsqueeze(-1)}
+    if return_rendered:                  # addition: the raw (H, W, 9) image the slices above are views of (lidar_rt_amd.losses works on it)
+        pkg["rendered"] = rendered
+    return pkg

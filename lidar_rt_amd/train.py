@@ -58,6 +58,7 @@ def run(args) -> dict:
         if not hasattr(opt, k):
             raise SystemExit(f"--opt {k}: not an option of lidar_rt_amd.training.default_options()")
         setattr(opt, k, type(getattr(opt, k))(float(v)) if not isinstance(getattr(opt, k), bool) else v.lower() in ("1", "true"))
+    opt.fused_loss = bool(opt.fused_loss or args.fused_loss)
     opt.iterations = max(opt.iterations, args.iters)
     torch.manual_seed(args.seed)
     scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed)
@@ -137,6 +138,8 @@ def main(argv=None) -> int:
                     "the pieces of long runs in order, the forward keeps no learnt tables): ~1.4 x the tracer time; a run resumed from a checkpoint then equals the "
                     "uninterrupted one bit for bit (with lambda_cd = 0: the Chamfer backward adds with float atomics).  SH tables of at most 17 coefficients per "
                     "channel (sh_degree <= 3 with a table sized for it): the backward raises otherwise")
+    ap.add_argument("--fused-loss", action="store_true", help="the depth / intensity / ray-drop losses and their gradient through the fused HIP operator "
+                    "(lidar_rt_amd.losses.range_image_loss: three launches, no float atomics) instead of the PyTorch expression")
     ap.add_argument("--refine-poses", action="store_true", help="also learn a per-frame se(3) correction of the recorded sensor poses through the tracer's "
                     "ray gradients (lidar_rt_amd.poses); written as poses<it>.pth beside each checkpoint and read back by --resume")
     ap.add_argument("--pose-lr-trans", type=float, default=1e-3, help="--refine-poses: Adam learning rate of the translation part (m)")

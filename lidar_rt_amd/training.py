@@ -40,7 +40,8 @@ def default_options() -> SimpleNamespace:
         densify_scale_threshold=0.0002, densify_grad_threshold=0.0002, densify_weight_threshold=0.0,
         prune_size_threshold=0.1, thresh_opa_prune=0.003, lambda_cd=0.01, lambda_depth_l1=0.1, lambda_intensity_l1=0.85,
         lambda_intensity_l2=0.0, lambda_intensity_dssim=0.15, lambda_raydrop_bce=0.01, lambda_reg=0.01, use_rayhit=False,
-        bvh_refit_interval=0)   # not in the reference: K refits between full LBVH builds (renderer.raytracing), 0 = rebuild per call
+        bvh_refit_interval=0,   # not in the reference: K refits between full LBVH builds (renderer.raytracing), 0 = rebuild per call
+        fused_loss=False)       # not in the reference: the per-pixel losses through the fused HIP operator (lidar_rt_amd.losses.range_image_loss)
 
 
 def expon_lr(step: int, lr_init: float, lr_final: float, delay_mult: float = 1.0, delay_steps: int = 0,
@@ -458,7 +459,8 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
     ``box_poses`` (an ``actor_poses.ActorPoses`` installed on the scene's actors): the same for the actors' tracking boxes; on several ranks
     its corrections are verified identical after every step.
     ``chamfer_points_detached``: the reference builds both point clouds from numpy (lidar_sensor.py:182-183), so its
-    Chamfer term carries no gradient; False keeps the predicted points differentiable."""
+    Chamfer term carries no gradient; False keeps the predicted points differentiable.
+    ``opt.fused_loss`` (default off): on a HIP device the depth / intensity / ray-drop terms come from ``losses.range_image_loss``."""
     from .renderer import raytracing
     if opt.lambda_cd != 0:
         from .chamfer3D import chamfer_3DDist
@@ -504,6 +506,29 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
         loss.backward()
         return pkg, loss, loss_depth, loss_int, loss_drop, loss_cd
 
+    def attempt_fused():
+        """attempt() with the per-pixel losses (depth, intensity, ray drop) from lidar_rt_amd.losses.range_image_loss: one HIP operator on the raw
+        (H, W, 9) image whose backward writes d_rendered in the tracer's layout; Chamfer and the box regulariser as above"""
+        from .losses import range_image_loss
+        pkg = raytracing(frame, scene.gaussians_assets, sensor, background, args, return_rendered=True)
+        gt_depth = frames.get_depth(frame)
+        loss_px, loss_depth, loss_int, loss_drop, _ = range_image_loss(pkg["rendered"], gt_depth, frames.get_intensity(frame), frames.get_mask(frame), opt)
+        if opt.lambda_cd != 0:
+            depth = pkg["depth"].squeeze(-1)
+            pred_depth = depth.detach() if chamfer_points_detached else depth
+            gt_pts = sensor.inverse_projection_with_range(frame, gt_depth)
+            pred_pts = sensor.inverse_projection_with_range(frame, pred_depth)
+            d1, d2, _, _ = chamfer_3DDist()(pred_pts[None].contiguous(), gt_pts[None].contiguous())
+            loss_cd = opt.lambda_cd * (d1 + d2).mean() * 0.5
+        else:
+            loss_cd = torch.zeros((), device=gt_depth.device)
+        loss_reg = sum(opt.lambda_reg * g.box_reg_loss() for g in scene.gaussians_assets)
+        loss = loss_px + loss_cd + loss_reg
+        loss.backward()
+        return pkg, loss, loss_depth, loss_int, loss_drop, loss_cd
+
+    if getattr(opt, "fused_loss", False) and frames.get_depth(frame).is_cuda:
+        attempt = attempt_fused
     pkg, loss, loss_depth, loss_int, loss_drop, loss_cd = attempt()
     redone = 0
     if _rnd.sharded is not None and getattr(opt, "verify_sharded_step", True):
