@@ -12,6 +12,9 @@
   library with its own source list, content hash and stamp, so that the tracer library's ``source_hash()`` (which keys committed profiles)
   does not move with it.  Loaded by ``lidar_rt_amd.losses``.
 
+* ``csrc/liblrt_gridcd.so`` -- the Chamfer term on the range-image grid (``csrc/lrt_gridcd.hip``, C ABI ``include/lrt_gridcd.h``): a third product
+  library on the loss library's pattern (own source list, content hash and stamp).  Loaded by ``lidar_rt_amd.grid_chamfer``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -50,6 +53,11 @@ LOSS_LIB = os.path.join(CSRC, "liblrt_loss.so")
 LOSS_STAMP = os.path.join(CSRC, "liblrt_loss.srchash")
 LOSS_SOURCES = ["lrt_loss.hip"]
 LOSS_HEADERS = ["lrt_loss_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_loss.h")]
+# the grid Chamfer library: the same pattern once more
+GRIDCD_LIB = os.path.join(CSRC, "liblrt_gridcd.so")
+GRIDCD_STAMP = os.path.join(CSRC, "liblrt_gridcd.srchash")
+GRIDCD_SOURCES = ["lrt_gridcd.hip"]
+GRIDCD_HEADERS = ["lrt_gridcd_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_gridcd.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -116,6 +124,46 @@ def build_loss(force: bool = False, verbose: bool = False) -> str:
     if verbose:
         print(resources.table_md(res), flush=True)
     return LOSS_LIB
+
+
+def gridcd_source_hash() -> str:
+    """source_hash() of the grid Chamfer library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(GRIDCD_SOURCES + GRIDCD_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def gridcd_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(GRIDCD_LIB):
+        return True
+    try:
+        return open(GRIDCD_STAMP).read().strip() != gridcd_source_hash()
+    except OSError:
+        return True
+
+
+def build_gridcd(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_gridcd.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other two libraries."""
+    if force or gridcd_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", GRIDCD_LIB] \
+            + [os.path.join(CSRC, s) for s in GRIDCD_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(GRIDCD_STAMP, "w") as f:
+            f.write(gridcd_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(GRIDCD_LIB)} is up to date (sources {gridcd_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(GRIDCD_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return GRIDCD_LIB
 
 
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
@@ -214,6 +262,7 @@ def _build_product(force: bool, verbose: bool) -> str:
         print(f"{sum(1 for n in res if resources.is_own_kernel(n))} kernels of this project in {os.path.basename(lib)}, none spills", flush=True)
     build_ext(force, verbose)
     build_loss(force, verbose)
+    build_gridcd(force, verbose)
     return lib
 
 

@@ -59,6 +59,7 @@ def run(args) -> dict:
             raise SystemExit(f"--opt {k}: not an option of lidar_rt_amd.training.default_options()")
         setattr(opt, k, type(getattr(opt, k))(float(v)) if not isinstance(getattr(opt, k), bool) else v.lower() in ("1", "true"))
     opt.fused_loss = bool(opt.fused_loss or args.fused_loss)
+    opt.grid_chamfer = bool(opt.grid_chamfer or args.grid_chamfer)
     opt.iterations = max(opt.iterations, args.iters)
     torch.manual_seed(args.seed)
     scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed)
@@ -96,7 +97,7 @@ def run(args) -> dict:
         torch.manual_seed(args.seed * 1_000_003 + it)      # the densification's random draws: a function of (seed, iteration) on every rank
         frame = frame_of(args.seed, it, seq.train_frames)
         res = training.training_step(scene, seq.frames, frame, it, opt, bg, dynamic=bool(seq.meta.get("dynamic")), poses=sensor_poses,
-                                      box_poses=box_poses)
+                                      box_poses=box_poses, chamfer_points_detached=not args.chamfer_grad)
         if it % args.log_every == 0 or it == args.iters:
             row = {"iteration": it, "frame": int(frame), "loss": float(res["loss"]), "depth": float(res["depth"]), "intensity": float(res["intensity"]),
                    "raydrop": float(res["raydrop"]), "points": int(res["points"]), "seconds": round(time.perf_counter() - t0, 3)}
@@ -136,10 +137,16 @@ def main(argv=None) -> int:
                     "the backward (renderer.deferred_accum, the default here: the loop reads them after the backward only)")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible steps (Tracer(deterministic=True): the backward adds a Gaussian's records up by ray and "
                     "the pieces of long runs in order, the forward keeps no learnt tables): ~1.4 x the tracer time; a run resumed from a checkpoint then equals the "
-                    "uninterrupted one bit for bit (with lambda_cd = 0: the Chamfer backward adds with float atomics).  SH tables of at most 17 coefficients per "
+                    "uninterrupted one bit for bit (with lambda_cd = 0, or with --grid-chamfer for lambda_cd != 0: chamfer_3DDist's backward adds with float atomics, "
+                    "the grid operator's does not).  SH tables of at most 17 coefficients per "
                     "channel (sh_degree <= 3 with a table sized for it): the backward raises otherwise")
     ap.add_argument("--fused-loss", action="store_true", help="the depth / intensity / ray-drop losses and their gradient through the fused HIP operator "
                     "(lidar_rt_amd.losses.range_image_loss: three launches, no float atomics) instead of the PyTorch expression")
+    ap.add_argument("--grid-chamfer", action="store_true", help="the Chamfer term (lambda_cd != 0) through the operator on the range-image grid "
+                    "(lidar_rt_amd.grid_chamfer.grid_chamfer: an exact tiled search, no sort, no tree, no float atomics) instead of chamfer_3DDist on the masked points; "
+                    "works with --fused-loss, --refine-poses, --refine-boxes and --gpus N (every rank computes the identical term on the gathered image)")
+    ap.add_argument("--chamfer-grad", action="store_true", help="keep the predicted points of the Chamfer term differentiable (chamfer_points_detached=False); "
+                    "the reference's term, and the default here, is a logged constant")
     ap.add_argument("--refine-poses", action="store_true", help="also learn a per-frame se(3) correction of the recorded sensor poses through the tracer's "
                     "ray gradients (lidar_rt_amd.poses); written as poses<it>.pth beside each checkpoint and read back by --resume")
     ap.add_argument("--pose-lr-trans", type=float, default=1e-3, help="--refine-poses: Adam learning rate of the translation part (m)")

@@ -41,7 +41,8 @@ def default_options() -> SimpleNamespace:
         prune_size_threshold=0.1, thresh_opa_prune=0.003, lambda_cd=0.01, lambda_depth_l1=0.1, lambda_intensity_l1=0.85,
         lambda_intensity_l2=0.0, lambda_intensity_dssim=0.15, lambda_raydrop_bce=0.01, lambda_reg=0.01, use_rayhit=False,
         bvh_refit_interval=0,   # not in the reference: K refits between full LBVH builds (renderer.raytracing), 0 = rebuild per call
-        fused_loss=False)       # not in the reference: the per-pixel losses through the fused HIP operator (lidar_rt_amd.losses.range_image_loss)
+        fused_loss=False,       # not in the reference: the per-pixel losses through the fused HIP operator (lidar_rt_amd.losses.range_image_loss)
+        grid_chamfer=False)     # not in the reference: the Chamfer term on the range-image grid (lidar_rt_amd.grid_chamfer.grid_chamfer)
 
 
 def expon_lr(step: int, lr_init: float, lr_final: float, delay_mult: float = 1.0, delay_steps: int = 0,
@@ -460,10 +461,16 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
     its corrections are verified identical after every step.
     ``chamfer_points_detached``: the reference builds both point clouds from numpy (lidar_sensor.py:182-183), so its
     Chamfer term carries no gradient; False keeps the predicted points differentiable.
-    ``opt.fused_loss`` (default off): on a HIP device the depth / intensity / ray-drop terms come from ``losses.range_image_loss``."""
+    ``opt.fused_loss`` (default off): on a HIP device the depth / intensity / ray-drop terms come from ``losses.range_image_loss``.
+    ``opt.grid_chamfer`` (default off): on a HIP device the Chamfer term comes from ``grid_chamfer.grid_chamfer`` on the frame's ray grid: the
+    same value as ``chamfer_3DDist`` on the masked points (the same nearest neighbours bit for bit, the means added up in float64), a backward
+    without float atomics (bit-reproducible), and an all-dropped frame gives 0 instead of an error."""
     from .renderer import raytracing
     if opt.lambda_cd != 0:
         from .chamfer3D import chamfer_3DDist
+    grid_cd = bool(getattr(opt, "grid_chamfer", False)) and opt.lambda_cd != 0 and frames.get_depth(frame).is_cuda
+    if grid_cd:
+        from .grid_chamfer import grid_chamfer
     scene.update_learning_rate(iteration)
     if iteration % 1000 == 0:
         scene.oneupSHdegree()
@@ -493,7 +500,10 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
                     + opt.lambda_intensity_dssim * (1 - ssim((intensity * mf).unsqueeze(0), (gt_int * mf).unsqueeze(0))))
         labels = (1.0 - mf).reshape(-1, 1)                                # 1 = dropped ray (train.py:188-193)
         loss_drop = opt.lambda_raydrop_bce * F.binary_cross_entropy(raydrop.reshape(-1, 1).clamp(1e-7, 1 - 1e-7), labels)
-        if opt.lambda_cd != 0:
+        if grid_cd:
+            pred_depth = depth.detach() if chamfer_points_detached else depth
+            loss_cd = grid_chamfer(*sensor.get_range_rays(frame), pred_depth, gt_depth, mask, weight=opt.lambda_cd)[0]
+        elif opt.lambda_cd != 0:
             pred_depth = depth.detach() if chamfer_points_detached else depth
             gt_pts = sensor.inverse_projection_with_range(frame, gt_depth)
             pred_pts = sensor.inverse_projection_with_range(frame, pred_depth)
@@ -513,7 +523,11 @@ def training_step(scene: GaussianScene, frames: RangeFrames, frame, iteration: i
         pkg = raytracing(frame, scene.gaussians_assets, sensor, background, args, return_rendered=True)
         gt_depth = frames.get_depth(frame)
         loss_px, loss_depth, loss_int, loss_drop, _ = range_image_loss(pkg["rendered"], gt_depth, frames.get_intensity(frame), frames.get_mask(frame), opt)
-        if opt.lambda_cd != 0:
+        if grid_cd:
+            depth = pkg["depth"].squeeze(-1)
+            pred_depth = depth.detach() if chamfer_points_detached else depth
+            loss_cd = grid_chamfer(*sensor.get_range_rays(frame), pred_depth, gt_depth, frames.get_mask(frame), weight=opt.lambda_cd)[0]
+        elif opt.lambda_cd != 0:
             depth = pkg["depth"].squeeze(-1)
             pred_depth = depth.detach() if chamfer_points_detached else depth
             gt_pts = sensor.inverse_projection_with_range(frame, gt_depth)

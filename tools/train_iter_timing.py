@@ -3,7 +3,10 @@
 share of the library's kernels in it (torch profiler, kernel names grouped).
 --fused-loss (or FUSED=1): the per-pixel losses through lidar_rt_amd.losses.range_image_loss.  --compare-loss: both settings in one process,
 alternating -- ms per iteration (median of RUNS >= 5 windows of 10 iterations each) and, profiled in a pass of its own, the GPU time and the
-launch count of the loss part alone (the raw image -> loss -> d_rendered, forward + backward), each as the median of RUNS passes."""
+launch count of the loss part alone (the raw image -> loss -> d_rendered, forward + backward), each as the median of RUNS passes.
+--compare-chamfer: the same alternating windows for the Chamfer term, chamfer_3DDist on the masked points against the grid operator
+(lidar_rt_amd.grid_chamfer), both with chamfer_points_detached=False; then the operator alone, forward and backward GPU time and launches,
+on this scene's coherent frame and on independent random ranges (the degenerate search)."""
 import os, sys, time, types
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
@@ -75,6 +78,69 @@ if "--compare-loss" in sys.argv:
     print(f"| loss part, GPU kernel time, us | {part[False][0]:.1f} (min {part[False][2]:.1f}, max {part[False][3]:.1f}) | {part[True][0]:.1f} (min {part[True][2]:.1f}, max {part[True][3]:.1f}) |")
     print(f"| loss part, kernel launches | {part[False][1]:.0f} | {part[True][1]:.0f} |")
     print(f"| loss part, share of the iteration's wall time (GPU time / iteration) | {part[False][0] / 10 / statistics.median(ms[False]):.1f} % | {part[True][0] / 10 / statistics.median(ms[True]):.1f} % |")
+    sys.exit(0)
+if "--compare-chamfer" in sys.argv:
+    import statistics
+    from torch.profiler import profile, ProfilerActivity
+    from lidar_rt_amd import grid_chamfer as gcd
+    from lidar_rt_amd.chamfer3D import chamfer_3DDist
+    runs = max(5, int(os.environ.get("RUNS", "7")))
+    it = 0
+    ms = {False: [], True: []}
+    for grid in (False, True):
+        opt.grid_chamfer = grid
+        for _ in range(3):
+            it += 1; training.training_step(scene, frames, 0, it, opt, bg, chamfer_points_detached=False)
+    for _ in range(runs):
+        for grid in (False, True):
+            opt.grid_chamfer = grid
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(10):
+                it += 1; training.training_step(scene, frames, 0, it, opt, bg, chamfer_points_detached=False)
+            torch.cuda.synchronize(); ms[grid].append((time.perf_counter() - t0) / 10 * 1e3)
+    with torch.no_grad():
+        pred = raytracing(0, scene.gaussians_assets, frames, bg, args)["depth"].squeeze(-1).detach().clone()
+    o_, d_ = frames.get_range_rays(0)
+    gt_d, mask = frames.get_depth(0), frames.get_mask(0)
+    gen = torch.Generator(device=dev).manual_seed(3)
+    clouds = {"coherent (this scene's prediction against its ground truth)": (pred, gt_d),
+              "incoherent (independent random ranges, 1-80 m)": (1 + 79 * torch.rand(pred.shape, device=dev, generator=gen), 1 + 79 * torch.rand(pred.shape, device=dev, generator=gen))}
+
+    def existing(ra, rb):
+        a = frames.inverse_projection_with_range(0, ra); b = frames.inverse_projection_with_range(0, rb)
+        d1, d2, _, _ = chamfer_3DDist()(a[None].contiguous(), b[None].contiguous())
+        return opt.lambda_cd * (d1 + d2).mean() * 0.5
+
+    def grid_op(ra, rb):
+        return gcd.grid_chamfer(o_, d_, ra, rb, mask, weight=opt.lambda_cd)[0]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            out = fn()
+            torch.cuda.synchronize()
+        ev = [e for e in prof.key_averages() if e.device_time_total > 0]
+        return out, sum(e.device_time_total for e in ev), sum(e.count for e in ev)
+    print(f"S1M, {pred.shape[0]} x {pred.shape[1]} image, {int(mask.sum())} valid pixels, {runs} alternating windows of 10 iterations, chamfer_points_detached=False")
+    print("| | chamfer_3DDist on the masked points (default) | grid operator (--grid-chamfer) |")
+    print("|---|---:|---:|")
+    f = lambda v: f"{statistics.median(v):.3f} (min {min(v):.3f}, max {max(v):.3f})"
+    print(f"| training iteration, ms wall | {f(ms[False])} | {f(ms[True])} |")
+    for name, (ra, rb) in clouds.items():
+        row = {}
+        for grid, fn in ((False, existing), (True, grid_op)):
+            fw, bw = [], []
+            for k in range(runs + 2):
+                x = ra.clone().requires_grad_(True)
+                loss, us_f, n_f = timed(lambda: fn(x, rb))
+                _, us_b, n_b = timed(lambda: loss.backward())
+                if k >= 2:
+                    fw.append((us_f, n_f)); bw.append((us_b, n_b))
+            med = lambda v: (statistics.median(u for u, _ in v), statistics.median(n for _, n in v), min(u for u, _ in v), max(u for u, _ in v))
+            row[grid] = (med(fw), med(bw))
+        for i, part in enumerate(("forward", "backward")):
+            c = lambda g: f"{row[g][i][0]:.1f} us (min {row[g][i][2]:.1f}, max {row[g][i][3]:.1f}), {row[g][i][1]:.0f} launches"
+            print(f"| operator alone, {name}: {part} (points included) | {c(False)} | {c(True)} |")
     sys.exit(0)
 for it in range(1, 4):
     training.training_step(scene, frames, 0, it, opt, bg)
