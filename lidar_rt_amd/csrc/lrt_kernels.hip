@@ -189,6 +189,7 @@ struct lrt_state {
     unsigned* bounds;    // 3 x 6 ordered-uint (min xyz, max xyz): read by this build / accumulated for the next / armed for the one after
     int bounds_sel, bounds_ready, lag_bounds;
     int order_P;        // vals_b holds the Morton order of the last FULL sort of this many primitives (lrt_refit, carried builds, the cull index), else -1
+    int sort_key_bytes; // width of the keys that full sort wrote (4: key32 and the own radix sort, 8 otherwise); they pair with vals_b in keys_b (lrt_debug_read 9)
     // carried order (round 6): builds of an unchanged number of primitives keep the last full sort's permutation -- parameters move by an optimizer
     // step between builds -- until it is `carry_max_age` builds old or more than carry_max_inv per mille of the neighbours in it are out of Morton
     // order (counted by k_make_tree, published with the forward's status words)
@@ -1160,6 +1161,8 @@ int lrt_get_stats(lrt_state* st, uint64_t out[8], void* stream_)
 
 /* Debug/test hook (not part of the drop-in surface): copy an internal buffer of the current build to the host.
  * which: 0 = sorted order (P x u32), 1 = records (P x 16 f32), 2 = nodes (n_nodes x 64 f32), 3 = aabbs (P x 6 f32).
+ * 9 = the sorted keys of the last full sort, which pair with the sorted order (P x u32 = Morton code >> 31 when the build wrote 32-bit keys:
+ *     key32 and the own radix sort; P x u64 otherwise); LRT_ERR_STATE after a build that carried the previous order (no sort ran).
  * Returns the number of bytes available (copies min(available, max_bytes)); synchronises `stream`. */
 long long lrt_debug_read(lrt_state* st, int which, void* host_dst, long long max_bytes, void* stream_)
 {
@@ -1178,6 +1181,10 @@ long long lrt_debug_read(lrt_state* st, int which, void* host_dst, long long max
         case 6: src = st->hit_t; bytes = (long long)st->hit_rays_cap * st->hit_cap_alloc * 4; break;      // their depths, [ray][hit_cap]
         case 7: src = st->hit_g; bytes = (long long)st->hit_rays_cap * st->hit_cap_alloc * 4; break;      // their Gaussians
         case 8: src = st->hit_wa; bytes = (long long)st->hit_rays_cap * st->hit_cap_alloc * 8; break;     // their (composite weight, un-clamped opacity x G) (deferred-colour forward)
+        case 9:                                                                                           // the keys beside vals_b (after the build's pointer swap: always keys_b)
+            if (st->carry_age > 0 || st->order_P != st->P_built || !st->sort_key_bytes)
+                LRT_FAIL(LRT_ERR_STATE, "lrt_debug_read: buffer 9 (sorted keys) needs a build that sorted all its primitives; the last one carried the previous order or was ray-culled (option carry_order = 0: every build sorts)");
+            src = st->keys_b; bytes = (long long)st->P_built * st->sort_key_bytes; break;
         default: LRT_FAIL(LRT_ERR_ARG, "lrt_debug_read: unknown buffer %d", which);
     }
     long long n = bytes < max_bytes ? bytes : max_bytes;
@@ -1234,7 +1241,7 @@ static int sort_all(const char* fn, lrt_state* st, int P, const float* means, co
         HIPCHK(lrt_rec_flush(st->lrec, stream));                    // rocPRIM launches by itself: what was recorded so far goes first, the rest of the call is eager
         HIPCHK(rocprim::radix_sort_pairs<lrt_build_sort_cfg>(st->sort_tmp, tmp, st->keys_a, st->keys_b, st->vals_a, st->vals_b, (size_t)P, 63 - sort_bits, 63, stream));
     }
-    st->order_P = P; st->carry_age = 0; st->carry_stale = 0;
+    st->order_P = P; st->carry_age = 0; st->carry_stale = 0; st->sort_key_bytes = key32 ? 4 : 8;
     st->pack_valid = pack ? 1 : 0;
     // leaf-sized Morton cells for the order-decay counter: the top log2(P) - 3 bits of the 63-bit code (8 primitives per cell on average)
     st->cell_shift = 63 - (pbits > 6 ? pbits - 3 : 3);

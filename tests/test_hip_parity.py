@@ -337,7 +337,8 @@ def test_own_radix_sort_and_rocprim_give_the_same_results():
 
 
 def _read_build(tr, which, n_bytes):
-    """Internal buffer of the current build (lrt_debug_read: 0 sorted order, 1 records, 2 SoA nodes)."""
+    """Internal buffer of the current build (lrt_debug_read: 0 sorted order, 1 records, 2 SoA nodes, 9 the sorted keys of the last full sort:
+    4 bytes each when the build wrote 32-bit keys, 8 otherwise)."""
     import ctypes as C
     st = tr.optix_context
     _, h = st.handle(torch.device("cuda:0"))

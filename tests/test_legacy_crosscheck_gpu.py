@@ -20,7 +20,8 @@ SELECT = ["tests/test_hip_parity.py::test_s10k_forward_backward_match_oracle", "
           "tests/test_hip_parity.py::test_randomised_scenes_cr4_against_the_legacy_packet_kernel",
           "tests/test_hip_parity.py::test_backward_twice_through_one_forward", "tests/test_near_rays_gpu.py",
           "tests/test_chamfer_gpu.py::test_forward_bit_exact_lidar_frame", "tests/test_chamfer_gpu.py::test_exact_ties_keep_the_first_index",
-          "tests/test_deferred_accum_gpu.py::test_legacy_backward_modes_fill_the_weights_too"]
+          "tests/test_deferred_accum_gpu.py::test_legacy_backward_modes_fill_the_weights_too",
+          "tests/test_radix_sort_gpu.py::test_histogram_launch_of_its_own_gives_the_same_order"]
 
 
 def test_retired_kernel_generations_still_agree_with_the_oracle_and_the_product():
