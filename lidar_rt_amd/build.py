@@ -15,6 +15,9 @@
 * ``csrc/liblrt_gridcd.so`` -- the Chamfer term on the range-image grid (``csrc/lrt_gridcd.hip``, C ABI ``include/lrt_gridcd.h``): a third product
   library on the loss library's pattern (own source list, content hash and stamp).  Loaded by ``lidar_rt_amd.grid_chamfer``.
 
+* ``csrc/liblrt_init.so`` -- the scene initialisation from range images (``csrc/lrt_init.hip``, C ABI ``include/lrt_init.h``): a fourth product
+  library on the same pattern.  Loaded by ``lidar_rt_amd.scene_init``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -58,6 +61,11 @@ GRIDCD_LIB = os.path.join(CSRC, "liblrt_gridcd.so")
 GRIDCD_STAMP = os.path.join(CSRC, "liblrt_gridcd.srchash")
 GRIDCD_SOURCES = ["lrt_gridcd.hip"]
 GRIDCD_HEADERS = ["lrt_gridcd_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_gridcd.h")]
+# the scene-initialisation library: once more (it reads the grid Chamfer operator's arithmetic header; that one's hash does not read back)
+INIT_LIB = os.path.join(CSRC, "liblrt_init.so")
+INIT_STAMP = os.path.join(CSRC, "liblrt_init.srchash")
+INIT_SOURCES = ["lrt_init.hip"]
+INIT_HEADERS = ["lrt_init_math.h", "lrt_gridcd_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_init.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -166,6 +174,46 @@ def build_gridcd(force: bool = False, verbose: bool = False) -> str:
     return GRIDCD_LIB
 
 
+def init_source_hash() -> str:
+    """source_hash() of the scene-initialisation library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(INIT_SOURCES + INIT_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def init_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(INIT_LIB):
+        return True
+    try:
+        return open(INIT_STAMP).read().strip() != init_source_hash()
+    except OSError:
+        return True
+
+
+def build_init(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_init.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other three libraries."""
+    if force or init_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", INIT_LIB] \
+            + [os.path.join(CSRC, s) for s in INIT_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(INIT_STAMP, "w") as f:
+            f.write(init_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(INIT_LIB)} is up to date (sources {init_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(INIT_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return INIT_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -263,6 +311,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_ext(force, verbose)
     build_loss(force, verbose)
     build_gridcd(force, verbose)
+    build_init(force, verbose)
     return lib
 
 

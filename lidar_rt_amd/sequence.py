@@ -15,7 +15,10 @@ in-memory ``RangeFrames`` / ``GaussianScene`` of ``lidar_rt_amd.training``:
     DIR/init/background.npz, DIR/init/actor_00.npz ...   (optional) points (N,3) f32 [world / actor frame] | intensity (N,) f32
                                   | normals (N,3) f32 (optional): the initial point clouds (gaussian_model.py:155-184); without them the
                                   background is initialised from the back-projected returns of the training frames, an actor from
-                                  random points in its box.
+                                  random points in its box -- or, with ``scene_from_sequence(..., init_from_frames=True)``
+                                  (``train --init-from-frames``), every MISSING cloud comes from ``scene_init.init_clouds``: per-return
+                                  normals from the k nearest returns of each frame, the returns inside a tracking box moved to that
+                                  actor's frame, the background averaged per voxel (gs_loader.py:82-215).  Clouds under DIR/init still win.
 
 ``write_sequence`` is the writer (tools/make_sequence.py renders synthetic sequences of the BASELINE configs' shapes with it);
 ``load_sequence`` the reader; ``scene_from_sequence`` builds the Gaussian assets.  ``python -m lidar_rt_amd.train --data DIR`` is the loop.
@@ -137,15 +140,32 @@ def load_sequence(root: str, device="cuda", frames: Optional[Sequence[int]] = No
     return SimpleNamespace(meta=meta, frames=rf, boxes=boxes, init=init, train_frames=train, test_frames=test, root=root)
 
 
-def scene_from_sequence(seq: SimpleNamespace, max_sh_degree: int = 3, max_points: int = 2_000_000, seed: int = 0) -> GaussianScene:
+def scene_from_sequence(seq: SimpleNamespace, max_sh_degree: int = 3, max_points: int = 2_000_000, seed: int = 0, init_from_frames: bool = False,
+                        voxel_size: float = 0.15, k: int = 6) -> GaussianScene:
     """Gaussian assets for a loaded sequence (asset 0 = background, then one per tracking box; gs_loader.py:88-160): from DIR/init/*.npz
     where present, else the background from the back-projected valid returns of the training frames (sub-sampled to ``max_points``,
-    intensity as the DC colour) and an actor from 2000 random points in its box."""
+    intensity as the DC colour) and an actor from 2000 random points in its box.  ``init_from_frames``: the clouds DIR/init lacks come from
+    ``scene_init.init_clouds(seq, k, voxel_size, seed=seed)`` instead (normals, real actor returns, voxel mean; ``max_points`` still caps
+    the background; the background's extent is the reference's quantile rule where meta.json carries none)."""
     g = torch.Generator(device="cpu").manual_seed(seed)
     rf, dev = seq.frames, next(iter(seq.frames.depth.values())).device
     extent = float(seq.meta.get("extent", 1.0))
-    if "background" in seq.init:
-        c = seq.init["background"]
+    init = seq.init
+    if init_from_frames and any(n not in init for n in ["background"] + [f"actor_{a:02d}" for a in range(len(seq.boxes))]):
+        from . import scene_init
+        made = scene_init.init_clouds(seq, k=k, voxel_size=voxel_size, seed=seed)
+        init = {**made, **seq.init}                             # what DIR/init holds wins
+        # what came from the frames (rows; for an actor, how many of them are real returns): train.py logs it
+        seq.init_report = {n: {"points": int(c["points"].shape[0]), "real": int(c.get("real", c["points"].shape[0]))} for n, c in made.items() if n not in seq.init}
+        if "background" not in seq.init:
+            c = made["background"]
+            if "extent" not in seq.meta:
+                extent = float(c["extent"])
+            if c["points"].shape[0] > max_points:
+                sel = torch.randperm(c["points"].shape[0], generator=g)[:max_points].to(dev)
+                init["background"] = {"points": c["points"][sel], "intensity": c["intensity"][sel], "normals": c["normals"][sel]}
+    if "background" in init:
+        c = init["background"]
         pts, inten, nrm = c["points"], c["intensity"], c.get("normals")
     else:
         ps, it = [], []
@@ -159,8 +179,8 @@ def scene_from_sequence(seq: SimpleNamespace, max_sh_degree: int = 3, max_points
     assets = [GaussianAsset.from_points(pts, inten.clamp(0, 1), nrm, max_sh_degree=max_sh_degree, extent=extent)]
     for a, tb in enumerate(seq.boxes):
         name = f"actor_{a:02d}"
-        if name in seq.init:
-            c = seq.init[name]
+        if name in init:
+            c = init[name]
             p_, i_, n_ = c["points"], c["intensity"], c.get("normals")
         else:
             u = torch.rand((2000, 3), generator=g).to(dev)

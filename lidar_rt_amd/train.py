@@ -62,7 +62,11 @@ def run(args) -> dict:
     opt.grid_chamfer = bool(opt.grid_chamfer or args.grid_chamfer)
     opt.iterations = max(opt.iterations, args.iters)
     torch.manual_seed(args.seed)
-    scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed)
+    scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed, init_from_frames=bool(args.init_from_frames),
+                                         voxel_size=args.voxel_size, k=args.init_knn)
+    if args.init_from_frames and rank == 0:
+        print(json.dumps({"init_from_frames": {"voxel_size": args.voxel_size, "knn": args.init_knn,
+                                               "clouds": getattr(seq, "init_report", {})}}), flush=True)
     scene.training_setup(opt)
     first = 1
     sensor_poses = None
@@ -132,6 +136,11 @@ def main(argv=None) -> int:
     ap.add_argument("--log-every", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-points", type=int, default=2_000_000, help="cap of the background's initial point cloud")
+    ap.add_argument("--init-from-frames", action="store_true", help="build the initial clouds DATA/init lacks from the training frames (lidar_rt_amd.scene_init: "
+                    "normals from each return's k nearest returns, the returns inside a tracking box moved to that actor, the background averaged per voxel) "
+                    "instead of un-oriented back-projected returns and random points in the boxes; --max-points still caps the background")
+    ap.add_argument("--voxel-size", type=float, default=0.15, help="--init-from-frames: edge of the background's averaging voxels (m)")
+    ap.add_argument("--init-knn", type=int, default=6, help="--init-from-frames: neighbours per normal, the return itself included (3..8)")
     ap.add_argument("--opt", action="append", default=[], help="training option name=value (lidar_rt_amd.training.default_options)")
     ap.add_argument("--exact-accum", action="store_true", help="hit weights complete at the forward (the reference's contract) instead of written by "
                     "the backward (renderer.deferred_accum, the default here: the loop reads them after the backward only)")
@@ -159,6 +168,10 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.refine_boxes and not os.path.exists(os.path.join(args.data, "boxes.npz")):
         ap.error(f"--refine-boxes: {args.data} has no tracking boxes (boxes.npz)")
+    if not 3 <= args.init_knn <= 8:
+        ap.error("--init-knn: 3 <= K <= 8")
+    if not args.voxel_size > 0:
+        ap.error("--voxel-size must be positive")
     if args.refine_poses and args.gpus > 1:
         ap.error("--refine-poses needs ray gradients, which azimuth sharding (--gpus > 1) does not provide")
     if args.exact_accum and args.deterministic:
