@@ -18,6 +18,9 @@
 * ``csrc/liblrt_init.so`` -- the scene initialisation from range images (``csrc/lrt_init.hip``, C ABI ``include/lrt_init.h``): a fourth product
   library on the same pattern.  Loaded by ``lidar_rt_amd.scene_init``.
 
+* ``csrc/liblrt_metrics.so`` -- the fused evaluation metrics (``csrc/lrt_metrics.hip``, C ABI ``include/lrt_metrics.h``): a fifth product
+  library on the same pattern.  Loaded by ``lidar_rt_amd.metrics``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -66,6 +69,11 @@ INIT_LIB = os.path.join(CSRC, "liblrt_init.so")
 INIT_STAMP = os.path.join(CSRC, "liblrt_init.srchash")
 INIT_SOURCES = ["lrt_init.hip"]
 INIT_HEADERS = ["lrt_init_math.h", "lrt_gridcd_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_init.h")]
+# the evaluation-metrics library: once more
+METRICS_LIB = os.path.join(CSRC, "liblrt_metrics.so")
+METRICS_STAMP = os.path.join(CSRC, "liblrt_metrics.srchash")
+METRICS_SOURCES = ["lrt_metrics.hip"]
+METRICS_HEADERS = ["lrt_metrics_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_metrics.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -214,6 +222,46 @@ def build_init(force: bool = False, verbose: bool = False) -> str:
     return INIT_LIB
 
 
+def metrics_source_hash() -> str:
+    """source_hash() of the evaluation-metrics library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(METRICS_SOURCES + METRICS_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def metrics_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(METRICS_LIB):
+        return True
+    try:
+        return open(METRICS_STAMP).read().strip() != metrics_source_hash()
+    except OSError:
+        return True
+
+
+def build_metrics(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_metrics.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other four libraries."""
+    if force or metrics_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", METRICS_LIB] \
+            + [os.path.join(CSRC, s) for s in METRICS_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(METRICS_STAMP, "w") as f:
+            f.write(metrics_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(METRICS_LIB)} is up to date (sources {metrics_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(METRICS_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return METRICS_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -312,6 +360,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_loss(force, verbose)
     build_gridcd(force, verbose)
     build_init(force, verbose)
+    build_metrics(force, verbose)
     return lib
 
 

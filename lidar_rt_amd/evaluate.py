@@ -41,7 +41,7 @@ def run(args) -> dict:
     bg = torch.tensor([0.0, 0.0, 1.0], device=dev)          # the reference's background for (intensity, ray-hit, ray-drop): eval.py:104
     rargs = SimpleNamespace(dynamic=bool(seq.meta.get("dynamic")), opt=SimpleNamespace(use_rayhit=bool(getattr(opt, "use_rayhit", False))), pipe=SimpleNamespace())
     res = evaluation.evaluate(scene.gaussians_assets, seq.frames, frames, bg, rargs, raydrop_ratio=args.raydrop_ratio, use_gt_mask=args.use_gt_mask,
-                              max_depth=args.max_depth)
+                              max_depth=args.max_depth, fused=bool(args.fused_metrics))
     return {"iteration": int(iteration), "frames": [int(f) for f in frames], "mean": res["mean"], "per_frame": {str(k): v for k, v in res["frames"].items()}}
 
 
@@ -58,6 +58,7 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--boxes", default=None, help="refined actor boxes (boxes<it>.pth of python -m lidar_rt_amd.train --refine-boxes) to render with")
+    ap.add_argument("--fused-metrics", action="store_true", help="every frame's figures from the fused HIP operator (lidar_rt_amd.metrics) instead of the PyTorch expressions")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     args = ap.parse_args(argv)
     res = run(args)

@@ -115,11 +115,15 @@ def fscore(dist1: torch.Tensor, dist2: torch.Tensor, threshold: float = 0.001):
 
 
 def evaluate(gaussian_assets: Sequence, sensor, frame_ids: Sequence, background: torch.Tensor, args=None,
-             raydrop_ratio: float = 0.4, use_gt_mask: bool = False, max_depth: float = 80.0) -> Dict[str, object]:
+             raydrop_ratio: float = 0.4, use_gt_mask: bool = False, max_depth: float = 80.0, fused: bool = False) -> Dict[str, object]:
     """Per-frame metrics and their means (eval.py:370-470; `raydrop_ratio` 0.4 as eval.py:72).  `sensor` offers get_depth /
     get_intensity / get_mask / inverse_projection_with_range like ``training.RangeFrames``.  As in ``record_render`` the rendered
     depth and the clamped rendered intensity are multiplied by the ray-hit mask (ground-truth or predicted, eval.py:184, :224, :238)
-    before they are compared with the ground truth.  One device->host transfer at the end."""
+    before they are compared with the ground truth.  One device->host transfer at the end.  `fused`: every frame's figures from the
+    HIP operator of ``lidar_rt_amd.metrics`` (one row of an (F, N) table per frame, no host wait between the frames) instead of the PyTorch
+    expressions below; the same dictionary."""
+    if fused:
+        return _evaluate_fused(gaussian_assets, sensor, frame_ids, background, args, raydrop_ratio, use_gt_mask, max_depth)
     frame_ids = list(frame_ids)
     renders = render_frames(gaussian_assets, sensor, frame_ids, background, args)
     per_frame: Dict[object, Dict[str, Dict[str, torch.Tensor]]] = {}
@@ -146,4 +150,29 @@ def evaluate(gaussian_assets: Sequence, sensor, frame_ids: Sequence, background:
         for m in (per_frame[frame_ids[0]][g] if frame_ids else {}):
             xs = [out_frames[f][g][m] for f in frame_ids if out_frames[f][g][m] == out_frames[f][g][m]]
             mean.setdefault(g, {})[m] = sum(xs) / len(xs) if xs else float("nan")
+    return {"frames": out_frames, "mean": mean}
+
+
+def _evaluate_fused(gaussian_assets, sensor, frame_ids, background, args, raydrop_ratio, use_gt_mask, max_depth) -> Dict[str, object]:
+    """`evaluate` with each frame's row from ``metrics.frame_metrics``; the table comes to the host in one transfer and the NaN-skipping means are
+    formed there as in `evaluate`."""
+    from . import metrics
+    frame_ids = list(frame_ids)
+    renders = render_frames(gaussian_assets, sensor, frame_ids, background, args)
+    names = [gm for gm in metrics.ROW if gm not in metrics.EXTRAS]
+    out_frames: Dict[object, Dict[str, Dict[str, float]]] = {}
+    if frame_ids:
+        table = torch.empty((len(frame_ids), metrics.N), dtype=torch.float32, device=renders[frame_ids[0]]["depth"].device)
+        for i, f in enumerate(frame_ids):
+            metrics.frame_metrics(renders[f], sensor.get_depth(f), sensor.get_intensity(f), sensor.get_mask(f), rays=sensor.get_range_rays(f),
+                                  raydrop_ratio=raydrop_ratio, use_gt_mask=use_gt_mask, max_depth=max_depth, out=table[i])
+        rows = table.cpu().tolist()                                   # one transfer
+        for f, row in zip(frame_ids, rows):
+            for (g, m), v in zip(metrics.ROW, row):
+                if (g, m) not in metrics.EXTRAS:
+                    out_frames.setdefault(f, {}).setdefault(g, {})[m] = v
+    mean: Dict[str, Dict[str, float]] = {}
+    for g, m in (names if frame_ids else []):
+        xs = [out_frames[f][g][m] for f in frame_ids if out_frames[f][g][m] == out_frames[f][g][m]]
+        mean.setdefault(g, {})[m] = sum(xs) / len(xs) if xs else float("nan")
     return {"frames": out_frames, "mean": mean}
