@@ -178,7 +178,8 @@ int lrt_get_stats(lrt_state* st, uint64_t stats_out[8], void* stream);
 int lrt_enable_timing(lrt_state* st, int enable);
 int lrt_get_timing(lrt_state* st, double ms_sum[4], int count[4], void* stream);
 
-/* Debug/test hook: copy an internal buffer of the current build to the host (see lrt_kernels.hip; 0 = sorted order, 9 = the sorted keys beside it, 4 or 8 bytes each). */
+/* Debug/test hook: copy an internal buffer of the current build to the host (see lrt_kernels.hip; 0 = sorted order, 9 = the sorted keys beside it, 4 or 8 bytes each;
+ * 1 = records, 2 = the SoA copy of the nodes (the K-buffer fallback's), 10 = their AoS copy (the one the shipped forward walks), n_nodes x 64 floats each). */
 long long lrt_debug_read(lrt_state* st, int which, void* host_dst, long long max_bytes, void* stream);
 
 /* Tunables (0 = keep default). tile_w: rays per tile row (power of two <= 64; tile = 64 rays).

@@ -1163,6 +1163,9 @@ int lrt_get_stats(lrt_state* st, uint64_t out[8], void* stream_)
  * which: 0 = sorted order (P x u32), 1 = records (P x 16 f32), 2 = nodes (n_nodes x 64 f32), 3 = aabbs (P x 6 f32).
  * 9 = the sorted keys of the last full sort, which pair with the sorted order (P x u32 = Morton code >> 31 when the build wrote 32-bit keys:
  *     key32 and the own radix sort; P x u64 otherwise); LRT_ERR_STATE after a build that carried the previous order (no sort ran).
+ * 10 = the AoS copy of the nodes (n_nodes x 64 f32; child c of a node = words 8 c .. 8 c + 7: lo.x hi.x lo.y hi.y lo.z hi.z, pointer and flags as
+ *     int bits): the buffer the shipped forward walks (k_fwd_cr4, k_fwd_near, k_fwd_init); 2 is the SoA copy that only k_trace reads.  Like 2
+ *     it is read behind finish_tree_now, so the levels 4 and above are in place whether or not a forward has run since the build.
  * Returns the number of bytes available (copies min(available, max_bytes)); synchronises `stream`. */
 long long lrt_debug_read(lrt_state* st, int which, void* host_dst, long long max_bytes, void* stream_)
 {
@@ -1185,6 +1188,7 @@ long long lrt_debug_read(lrt_state* st, int which, void* host_dst, long long max
             if (st->carry_age > 0 || st->order_P != st->P_built || !st->sort_key_bytes)
                 LRT_FAIL(LRT_ERR_STATE, "lrt_debug_read: buffer 9 (sorted keys) needs a build that sorted all its primitives; the last one carried the previous order or was ray-culled (option carry_order = 0: every build sorts)");
             src = st->keys_b; bytes = (long long)st->P_built * st->sort_key_bytes; break;
+        case 10: src = st->nodes_aos; bytes = (long long)st->n_nodes * LRT_NODE_FLOATS * 4; break;        // the tree as the shipped forward reads it
         default: LRT_FAIL(LRT_ERR_ARG, "lrt_debug_read: unknown buffer %d", which);
     }
     long long n = bytes < max_bytes ? bytes : max_bytes;

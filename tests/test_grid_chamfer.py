@@ -30,8 +30,9 @@ def test_the_library_has_a_source_list_of_its_own_and_moves_no_other_hash():
     assert "lrt_gridcd.hip" in lrt_build.GRIDCD_SOURCES and "lrt_gridcd_math.h" in lrt_build.GRIDCD_HEADERS
     assert not any("gridcd" in f for f in lrt_build.SOURCES + lrt_build.HEADERS + lrt_build.LOSS_SOURCES + lrt_build.LOSS_HEADERS)
     # the values of the commits the other two libraries were last changed by: committed profiles are keyed by them (the tracer library's:
-    # 71ad66c6f4addc35 when this library was added, moved since by the sorted-key read-back of lrt_debug_read -- host code, no kernel changed)
-    assert lrt_build.source_hash() == "9fc2959dbdff92f5"
+    # 71ad66c6f4addc35 when this library was added, moved since by the sorted-key read-back of lrt_debug_read and then by
+    # its read-back of the AoS nodes (selector 10) -- host code, no kernel changed either time: tests/test_resources.py holds unchanged)
+    assert lrt_build.source_hash() == "ed0452e8b58addfb"
     assert lrt_build.loss_source_hash() == "cc56b0c83f72d5ca"
     assert lrt_build.gridcd_source_hash() not in (lrt_build.source_hash(), lrt_build.loss_source_hash())
     assert os.path.basename(lrt_build.GRIDCD_LIB) == "liblrt_gridcd.so" and lrt_build.GRIDCD_LIB not in (lrt_build.LIB, lrt_build.LOSS_LIB)
