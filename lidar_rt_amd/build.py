@@ -21,6 +21,9 @@
 * ``csrc/liblrt_metrics.so`` -- the fused evaluation metrics (``csrc/lrt_metrics.hip``, C ABI ``include/lrt_metrics.h``): a fifth product
   library on the same pattern.  Loaded by ``lidar_rt_amd.metrics``.
 
+* ``csrc/liblrt_adam.so`` -- the fused Adam step over an asset's parameter groups (``csrc/lrt_adam.hip``, C ABI ``include/lrt_adam.h``): a sixth product
+  library on the same pattern.  Loaded by ``lidar_rt_amd.optim``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -74,6 +77,11 @@ METRICS_LIB = os.path.join(CSRC, "liblrt_metrics.so")
 METRICS_STAMP = os.path.join(CSRC, "liblrt_metrics.srchash")
 METRICS_SOURCES = ["lrt_metrics.hip"]
 METRICS_HEADERS = ["lrt_metrics_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_metrics.h")]
+# the optimizer library: once more
+ADAM_LIB = os.path.join(CSRC, "liblrt_adam.so")
+ADAM_STAMP = os.path.join(CSRC, "liblrt_adam.srchash")
+ADAM_SOURCES = ["lrt_adam.hip"]
+ADAM_HEADERS = ["lrt_adam_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_adam.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -262,6 +270,46 @@ def build_metrics(force: bool = False, verbose: bool = False) -> str:
     return METRICS_LIB
 
 
+def adam_source_hash() -> str:
+    """source_hash() of the optimizer library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(ADAM_SOURCES + ADAM_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def adam_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(ADAM_LIB):
+        return True
+    try:
+        return open(ADAM_STAMP).read().strip() != adam_source_hash()
+    except OSError:
+        return True
+
+
+def build_adam(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_adam.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other five libraries."""
+    if force or adam_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", ADAM_LIB] \
+            + [os.path.join(CSRC, s) for s in ADAM_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(ADAM_STAMP, "w") as f:
+            f.write(adam_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(ADAM_LIB)} is up to date (sources {adam_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(ADAM_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return ADAM_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -361,6 +409,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_gridcd(force, verbose)
     build_init(force, verbose)
     build_metrics(force, verbose)
+    build_adam(force, verbose)
     return lib
 
 

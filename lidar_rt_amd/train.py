@@ -60,6 +60,8 @@ def run(args) -> dict:
         setattr(opt, k, type(getattr(opt, k))(float(v)) if not isinstance(getattr(opt, k), bool) else v.lower() in ("1", "true"))
     opt.fused_loss = bool(opt.fused_loss or args.fused_loss)
     opt.grid_chamfer = bool(opt.grid_chamfer or args.grid_chamfer)
+    opt.sparse_adam = bool(opt.sparse_adam or args.sparse_adam)
+    opt.fused_adam = bool(opt.fused_adam or args.fused_adam or opt.sparse_adam)
     opt.iterations = max(opt.iterations, args.iters)
     torch.manual_seed(args.seed)
     scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed, init_from_frames=bool(args.init_from_frames),
@@ -154,6 +156,13 @@ def main(argv=None) -> int:
     ap.add_argument("--grid-chamfer", action="store_true", help="the Chamfer term (lambda_cd != 0) through the operator on the range-image grid "
                     "(lidar_rt_amd.grid_chamfer.grid_chamfer: an exact tiled search, no sort, no tree, no float atomics) instead of chamfer_3DDist on the masked points; "
                     "works with --fused-loss, --refine-poses, --refine-boxes and --gpus N (every rank computes the identical term on the gathered image)")
+    ap.add_argument("--fused-adam", action="store_true", help="the optimizer step of every asset through the fused HIP operator (lidar_rt_amd.optim.GaussianAdam: "
+                    "one launch for the six parameter groups, no atomics) instead of torch.optim.Adam(fused=True); same rule, same state, checkpoints move "
+                    "between the two")
+    ap.add_argument("--sparse-adam", action="store_true", help="implies --fused-adam: step only the Gaussians the frame hit; an unseen Gaussian keeps its parameter and "
+                    "both Adam moments bit for bit (its moments do not decay, it does not coast).  An actor with a tracking box is stepped densely while "
+                    "lambda_reg != 0 (the box regulariser gives every row a gradient).  Works with --gpus N (the hit mask is identical on every rank) and "
+                    "keeps --deterministic's promise (no atomics, no history)")
     ap.add_argument("--chamfer-grad", action="store_true", help="keep the predicted points of the Chamfer term differentiable (chamfer_points_detached=False); "
                     "the reference's term, and the default here, is a logged constant")
     ap.add_argument("--refine-poses", action="store_true", help="also learn a per-frame se(3) correction of the recorded sensor poses through the tracer's "

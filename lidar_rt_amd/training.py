@@ -42,7 +42,9 @@ def default_options() -> SimpleNamespace:
         lambda_intensity_l2=0.0, lambda_intensity_dssim=0.15, lambda_raydrop_bce=0.01, lambda_reg=0.01, use_rayhit=False,
         bvh_refit_interval=0,   # not in the reference: K refits between full LBVH builds (renderer.raytracing), 0 = rebuild per call
         fused_loss=False,       # not in the reference: the per-pixel losses through the fused HIP operator (lidar_rt_amd.losses.range_image_loss)
-        grid_chamfer=False)     # not in the reference: the Chamfer term on the range-image grid (lidar_rt_amd.grid_chamfer.grid_chamfer)
+        grid_chamfer=False,     # not in the reference: the Chamfer term on the range-image grid (lidar_rt_amd.grid_chamfer.grid_chamfer)
+        fused_adam=False,       # not in the reference: the optimizer step of an asset through the fused HIP operator (lidar_rt_amd.optim.GaussianAdam)
+        sparse_adam=False)      # not in the reference: that step on the rows the frame hit only (implies fused_adam; GaussianScene.optimize)
 
 
 def expon_lr(step: int, lr_init: float, lr_final: float, delay_mult: float = 1.0, delay_steps: int = 0,
@@ -139,8 +141,13 @@ class GaussianAsset:
         pr = self._params()
         # same update rule as the reference's torch.optim.Adam(lr=0.0, eps=1e-15); on the GPU the fused implementation runs the
         # six groups in one multi-tensor kernel (1.45 -> 0.35 ms per step at 1 M Gaussians)
-        self.optimizer = torch.optim.Adam([{"params": [pr[n]], "lr": lrs[n], "name": n} for n in self.GROUPS], lr=0.0, eps=1e-15,
-                                          fused=bool(dev.type == "cuda"))
+        if getattr(opt, "fused_adam", False) or getattr(opt, "sparse_adam", False):
+            # the same rule and the same state layout from the package's own operator: one launch for the six groups (lidar_rt_amd.optim)
+            from .optim import GaussianAdam
+            self.optimizer = GaussianAdam([{"params": [pr[n]], "lr": lrs[n], "name": n} for n in self.GROUPS], lr=0.0, eps=1e-15)
+        else:
+            self.optimizer = torch.optim.Adam([{"params": [pr[n]], "lr": lrs[n], "name": n} for n in self.GROUPS], lr=0.0, eps=1e-15,
+                                              fused=bool(dev.type == "cuda"))
         self._lr_args = dict(lr_init=opt.position_lr_init * self.spatial_lr_scale, lr_final=opt.position_lr_final * self.spatial_lr_scale,
                              delay_mult=opt.position_lr_delay_mult, max_steps=opt.position_lr_max_steps)
 
@@ -328,7 +335,12 @@ class GaussianScene:
             g.restore(mp, opt)
 
     def optimize(self, opt, iteration: int, mean_grads: torch.Tensor, accum_weights: torch.Tensor):
-        """Densification statistics / densify & prune / opacity reset / Adam step per asset (gs_loader.py:243-298)."""
+        """Densification statistics / densify & prune / opacity reset / Adam step per asset (gs_loader.py:243-298).
+        ``opt.sparse_adam`` (default off; the assets then carry ``optim.GaussianAdam``): the step updates only the rows the frame hit
+        (``touched = accum_weights > 0``, identical on every rank); a row no ray hit keeps its parameter and both Adam moments bit for bit --
+        its moments do not decay and it does not coast along its first moment.  An asset with a tracking box and ``opt.lambda_reg != 0`` is
+        stepped densely all the same: ``box_reg_loss`` gives EVERY row of such an asset a gradient whether a ray hit it or not, and leaving the
+        unseen rows out would silently switch the regulariser off for them."""
         tot = [0, 0, 0, 0]
         begin = 0
         for g in self.gaussians_assets:
@@ -343,7 +355,10 @@ class GaussianScene:
                 if iteration % opt.opacity_reset_interval == 0:
                     g.reset_opacity()
             if iteration < opt.iterations:
-                g.optimizer.step()
+                if getattr(opt, "sparse_adam", False):
+                    g.optimizer.step(rows=None if (g.bounding_box is not None and opt.lambda_reg != 0) else touched)
+                else:
+                    g.optimizer.step()
                 g.optimizer.zero_grad(set_to_none=True)
         return tuple(tot)
 

@@ -6,7 +6,12 @@ alternating -- ms per iteration (median of RUNS >= 5 windows of 10 iterations ea
 launch count of the loss part alone (the raw image -> loss -> d_rendered, forward + backward), each as the median of RUNS passes.
 --compare-chamfer: the same alternating windows for the Chamfer term, chamfer_3DDist on the masked points against the grid operator
 (lidar_rt_amd.grid_chamfer), both with chamfer_points_detached=False; then the operator alone, forward and backward GPU time and launches,
-on this scene's coherent frame and on independent random ranges (the degenerate search)."""
+on this scene's coherent frame and on independent random ranges (the degenerate search).
+--compare-adam [--actors]: the same alternating windows for the optimizer step under three settings, each on a scene of its own: torch.optim.Adam
+(fused=True, the default), lidar_rt_amd.optim.GaussianAdam (--fused-adam) and GaussianAdam on the rows the frame hit (--fused-adam --sparse-adam);
+then, profiled in a pass of its own, the GPU kernel time and the launch count of the optimizer part alone (the steps of all assets on the
+gradients of one real backward), and the measured share of touched rows.  S1M by default; --actors: the kitti360_dynamic shape (500 k background
+Gaussians + 8 actors x 8 k with tracking boxes, 66 x 1030 rays), where sparse mode steps the boxed actors densely (lambda_reg != 0)."""
 import os, sys, time, types
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
@@ -14,6 +19,103 @@ from lidar_rt_amd import scenes, training
 from lidar_rt_amd.renderer import raytracing
 
 dev = torch.device("cuda:0")
+
+
+def compare_adam():
+    import statistics
+    from torch.profiler import profile, ProfilerActivity
+    t = lambda a: torch.as_tensor(a, device=dev)
+    runs = max(5, int(os.environ.get("RUNS", "7")))
+    with_actors = "--actors" in sys.argv
+    bg = torch.tensor([0.0, 0.0, 1.0], device=dev)
+
+    def mk(s, noise, seed, box=None):
+        r = np.random.default_rng(seed); op = s["opacities"]
+        a = training.GaussianAsset.from_tensors(t(s["means"] + noise * r.normal(size=s["means"].shape).astype(np.float32)), t(s["shs"][:, :1]), t(s["shs"][:, 1:]),
+                                                t(np.log(s["scales"])), t(s["rotations"]), t(np.log(op / (1 - op))), extent=60.0, bounding_box=box)
+        a.active_sh_degree = 3
+        return a
+    if with_actors:
+        bgs, acts, poses_of, rays_of = scenes.kitti360_dynamic()
+        ro, rd = rays_of(0)
+        poses = poses_of(0)
+        lo, hi = t(np.array([-2.3, -1.05, -0.1], np.float32)), t(np.array([2.3, 1.05, 1.7], np.float32))     # the actors' 4.4 x 1.9 x 1.6 m box with a margin
+
+        def assets(noise):
+            out = [mk(bgs, noise, 1)]
+            for k, (a, (tt, q)) in enumerate(zip(acts, poses)):
+                out.append(mk(a, noise, 2 + k, types.SimpleNamespace(frame={0: (t(tt), t(q).reshape(1, 4), None, None)}, min_xyz=lo, max_xyz=hi)))
+            return out
+        shape = f"kitti360_dynamic: {bgs['means'].shape[0]} background Gaussians + {len(acts)} boxed actors x {acts[0]['means'].shape[0]}"
+    else:
+        s1, ro, rd = scenes.s1m()
+        assets = lambda noise: [mk(s1, noise, 1)]
+        shape = f"S1M: {s1['means'].shape[0]} Gaussians, one asset"
+    base = training.default_options()
+    args = types.SimpleNamespace(dynamic=with_actors, opt=base, pipe=types.SimpleNamespace())
+    frames = training.RangeFrames()
+    with torch.no_grad():
+        pk = raytracing(0, assets(0.0), (t(ro), t(rd), t(ro[0, 0])), bg, args)
+    frames.add_frame(0, t(ro), t(rd), pk["depth"].squeeze(-1).detach(), pk["intensity"].squeeze(-1).detach(), pk["raydrop"].squeeze(-1) < 0.6)
+    settings = (("torch.optim.Adam(fused=True) (default)", {}), ("GaussianAdam (--fused-adam)", {"fused_adam": True}),
+                ("GaussianAdam, hit rows (--fused-adam --sparse-adam)", {"fused_adam": True, "sparse_adam": True}))
+    opts, scs = [], []
+    for _, kw in settings:
+        o = types.SimpleNamespace(**vars(base))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        sc_ = training.GaussianScene(assets(0.02)); sc_.training_setup(o)
+        opts.append(o); scs.append(sc_)
+    it = 0
+    step = lambda k, o=None: training.training_step(scs[k], frames, 0, it, o or opts[k], bg, dynamic=with_actors)
+    for k in range(3):                                            # warm every path (code objects, workspaces, allocator)
+        for _ in range(3):
+            it += 1; step(k)
+    ms = [[], [], []]
+    for _ in range(runs):                                         # alternating windows: drift of the machine hits all three alike
+        for k in range(3):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(10):
+                it += 1; step(k)
+            torch.cuda.synchronize(); ms[k].append((time.perf_counter() - t0) / 10 * 1e3)
+    # the optimizer part alone: one real backward whose optimizer step is left out (iterations = 0) leaves the gradients in place; the rows it
+    # touched are those whose densification count moved.  Then the steps of all assets, profiled (profiler on: no wall time taken here)
+    part, share = [], None
+    for k in range(3):
+        hold = types.SimpleNamespace(**vars(opts[k])); hold.iterations = 0
+        before = [g.denom.clone() for g in scs[k].gaussians_assets]
+        it += 1; step(k, hold)
+        touched = [((g.denom - b) > 0).reshape(-1) for g, b in zip(scs[k].gaussians_assets, before)]
+        if share is None:
+            share = [float(x.float().mean()) for x in touched]
+        us, launches = [], []
+        for r in range(runs + 2):
+            torch.cuda.synchronize()
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                for g, rows in zip(scs[k].gaussians_assets, touched):
+                    if getattr(opts[k], "sparse_adam", False):
+                        g.optimizer.step(rows=None if (g.bounding_box is not None and opts[k].lambda_reg != 0) else rows)
+                    else:
+                        g.optimizer.step()
+                torch.cuda.synchronize()
+            if r >= 2:
+                ev = [e for e in prof.key_averages() if e.device_time_total > 0]
+                us.append(sum(e.device_time_total for e in ev)); launches.append(sum(e.count for e in ev))
+        part.append((statistics.median(us), statistics.median(launches), min(us), max(us)))
+    print(f"{shape}; {ro.shape[0]} x {ro.shape[1]} rays; {runs} alternating windows of 10 iterations; optimizer part: {runs} profiled passes")
+    print(f"touched rows of the frame (accum_weights > 0): " + ", ".join(f"{'background' if i == 0 else f'actor {i}'} {100 * x:.1f} %" for i, x in enumerate(share)))
+    print("| | " + " | ".join(n for n, _ in settings) + " |")
+    print("|---|---:|---:|---:|")
+    f = lambda v: f"{statistics.median(v):.3f} (min {min(v):.3f}, max {max(v):.3f})"
+    print("| training iteration, ms wall | " + " | ".join(f(v) for v in ms) + " |")
+    print("| optimizer part, GPU kernel time, us | " + " | ".join(f"{p[0]:.1f} (min {p[2]:.1f}, max {p[3]:.1f})" for p in part) + " |")
+    print("| optimizer part, kernel launches | " + " | ".join(f"{p[1]:.0f}" for p in part) + " |")
+    print("| optimizer part, share of the iteration's wall time (GPU time / iteration) | " + " | ".join(f"{p[0] / 10 / statistics.median(v):.1f} %" for p, v in zip(part, ms)) + " |")
+
+
+if "--compare-adam" in sys.argv:
+    compare_adam()
+    sys.exit(0)
 sc, ro, rd = scenes.s1m()
 t = lambda a: torch.as_tensor(a, device=dev)
 op = sc["opacities"]
