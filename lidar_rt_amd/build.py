@@ -24,6 +24,9 @@
 * ``csrc/liblrt_adam.so`` -- the fused Adam step over an asset's parameter groups (``csrc/lrt_adam.hip``, C ABI ``include/lrt_adam.h``): a sixth product
   library on the same pattern.  Loaded by ``lidar_rt_amd.optim``.
 
+* ``csrc/liblrt_densify.so`` -- the fused densify-and-prune of an asset (``csrc/lrt_densify.hip``, C ABI ``include/lrt_densify.h``): a seventh product
+  library on the same pattern.  Loaded by ``lidar_rt_amd.densify``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -82,6 +85,11 @@ ADAM_LIB = os.path.join(CSRC, "liblrt_adam.so")
 ADAM_STAMP = os.path.join(CSRC, "liblrt_adam.srchash")
 ADAM_SOURCES = ["lrt_adam.hip"]
 ADAM_HEADERS = ["lrt_adam_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_adam.h")]
+# the densification library: once more
+DENSIFY_LIB = os.path.join(CSRC, "liblrt_densify.so")
+DENSIFY_STAMP = os.path.join(CSRC, "liblrt_densify.srchash")
+DENSIFY_SOURCES = ["lrt_densify.hip"]
+DENSIFY_HEADERS = ["lrt_densify_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_densify.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -310,6 +318,46 @@ def build_adam(force: bool = False, verbose: bool = False) -> str:
     return ADAM_LIB
 
 
+def densify_source_hash() -> str:
+    """source_hash() of the densification library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(DENSIFY_SOURCES + DENSIFY_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def densify_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(DENSIFY_LIB):
+        return True
+    try:
+        return open(DENSIFY_STAMP).read().strip() != densify_source_hash()
+    except OSError:
+        return True
+
+
+def build_densify(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_densify.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other six libraries."""
+    if force or densify_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", DENSIFY_LIB] \
+            + [os.path.join(CSRC, s) for s in DENSIFY_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(DENSIFY_STAMP, "w") as f:
+            f.write(densify_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(DENSIFY_LIB)} is up to date (sources {densify_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(DENSIFY_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return DENSIFY_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -410,6 +458,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_init(force, verbose)
     build_metrics(force, verbose)
     build_adam(force, verbose)
+    build_densify(force, verbose)
     return lib
 
 

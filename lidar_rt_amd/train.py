@@ -62,6 +62,7 @@ def run(args) -> dict:
     opt.grid_chamfer = bool(opt.grid_chamfer or args.grid_chamfer)
     opt.sparse_adam = bool(opt.sparse_adam or args.sparse_adam)
     opt.fused_adam = bool(opt.fused_adam or args.fused_adam or opt.sparse_adam)
+    opt.fused_densify = bool(getattr(opt, "fused_densify", False) or args.fused_densify)
     opt.iterations = max(opt.iterations, args.iters)
     torch.manual_seed(args.seed)
     scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed, init_from_frames=bool(args.init_from_frames),
@@ -163,6 +164,10 @@ def main(argv=None) -> int:
                     "both Adam moments bit for bit (its moments do not decay, it does not coast).  An actor with a tracking box is stepped densely while "
                     "lambda_reg != 0 (the box regulariser gives every row a gradient).  Works with --gpus N (the hit mask is identical on every rank) and "
                     "keeps --deterministic's promise (no atomics, no history)")
+    ap.add_argument("--fused-densify", action="store_true", help="the densification statistics and densify-and-prune of every asset through the fused HIP "
+                    "operator (lidar_rt_amd.densify: one launch per asset and iteration for the statistics; an event is one decision per row and one "
+                    "compaction of the asset -- four launches and one host wait) instead of the PyTorch bookkeeping; the same rule and row order, the normal "
+                    "draws made up front from the iteration's seed.  Works with --fused-adam, --sparse-adam, --deterministic and --gpus N")
     ap.add_argument("--chamfer-grad", action="store_true", help="keep the predicted points of the Chamfer term differentiable (chamfer_points_detached=False); "
                     "the reference's term, and the default here, is a logged constant")
     ap.add_argument("--refine-poses", action="store_true", help="also learn a per-frame se(3) correction of the recorded sensor poses through the tracer's "

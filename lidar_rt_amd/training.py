@@ -44,7 +44,8 @@ def default_options() -> SimpleNamespace:
         fused_loss=False,       # not in the reference: the per-pixel losses through the fused HIP operator (lidar_rt_amd.losses.range_image_loss)
         grid_chamfer=False,     # not in the reference: the Chamfer term on the range-image grid (lidar_rt_amd.grid_chamfer.grid_chamfer)
         fused_adam=False,       # not in the reference: the optimizer step of an asset through the fused HIP operator (lidar_rt_amd.optim.GaussianAdam)
-        sparse_adam=False)      # not in the reference: that step on the rows the frame hit only (implies fused_adam; GaussianScene.optimize)
+        sparse_adam=False,      # not in the reference: that step on the rows the frame hit only (implies fused_adam; GaussianScene.optimize)
+        fused_densify=False)    # not in the reference: densification statistics and densify-and-prune through the fused HIP operator (lidar_rt_amd.densify)
 
 
 def expon_lr(step: int, lr_init: float, lr_final: float, delay_mult: float = 1.0, delay_steps: int = 0,
@@ -135,6 +136,7 @@ class GaussianAsset:
     def training_setup(self, opt):
         P, dev = self._xyz.shape[0], self._xyz.device
         self.densify_scale_threshold, self.densify_weight_threshold = opt.densify_scale_threshold, opt.densify_weight_threshold
+        self.fused_densify = bool(getattr(opt, "fused_densify", False))
         self.xyz_gradient_accum, self.denom = torch.zeros((P, 1), device=dev), torch.zeros((P, 1), device=dev)
         lrs = {"xyz": opt.position_lr_init * self.spatial_lr_scale, "f_dc": opt.feature_lr, "f_rest": opt.feature_lr / 20.0,
                "opacity": opt.opacity_lr, "scaling": opt.scaling_lr, "rotation": opt.rotation_lr}
@@ -197,6 +199,11 @@ class GaussianAsset:
 
     # ---- densification --------------------------------------------------------------------------------------------
     def add_densification_stats(self, mean_grads: torch.Tensor, update_filter: torch.Tensor):
+        """``update_filter``: the rows a ray hit, as a bool mask or (under ``opt.fused_densify``, which takes one launch for both columns) as the
+        iteration's hit weights themselves."""
+        if getattr(self, "fused_densify", False):
+            from .densify import densify_stats
+            return densify_stats(self.xyz_gradient_accum, self.denom, mean_grads, update_filter)
         self.xyz_gradient_accum += torch.norm(mean_grads, dim=-1, keepdim=True)
         self.denom += update_filter.reshape(-1, 1).to(self.denom.dtype)       # == denom[update_filter] += 1, without nonzero()
 
@@ -206,6 +213,8 @@ class GaussianAsset:
     def densify_and_prune(self, opt, size_limit: Optional[float]) -> Tuple[int, int, int, int]:
         """Clone small / split large Gaussians whose mean positional gradient is above the threshold, then prune
         transparent, oversized and (for actors) out-of-box ones (gaussian_model.py:311-411)."""
+        if getattr(opt, "fused_densify", False):
+            return self._densify_fused(opt, size_limit)
         grads = (self.xyz_gradient_accum / self.denom).nan_to_num(0.0).squeeze(-1)
         big = torch.max(self.get_scaling, dim=1).values > self.densify_scale_threshold * self.extent
         # clone: copies of the selected Gaussians are appended unchanged
@@ -237,6 +246,36 @@ class GaussianAsset:
         if int(mask.sum()) < self._xyz.shape[0]:
             self.prune_points(mask)
         return n_clone, n_split, n_scale, n_opa
+
+    def _densify_fused(self, opt, size_limit) -> Tuple[int, int, int, int]:
+        """densify_and_prune as ONE decision per row and one compaction (lidar_rt_amd.densify; include/lrt_densify.h states the rule): the same
+        clone / split / prune rule and the same row order, with the normal draws made up front -- ``(P, 2, 3)`` for the children, ``(P, 2, 2, 3)``
+        for an actor's box samples, from the default generator on the asset's device, so they stay a function of the seed train.py sets per
+        iteration.  The result is installed the way ``_rewrite`` installs one: new Parameters without a gradient, the Adam state moved over with
+        ``step`` kept."""
+        from . import densify as dn
+        P, dev = self._xyz.shape[0], self._xyz.device
+        bb = self.bounding_box
+        if bb is not None and getattr(self, "_box_host", (None,))[0] is not bb.min_xyz:
+            self._box_host = (bb.min_xyz, SimpleNamespace(min_xyz=torch.as_tensor(bb.min_xyz).reshape(-1).tolist(), max_xyz=torch.as_tensor(bb.max_xyz).reshape(-1).tolist()))
+        rule = dn.rule_of(opt, self.extent, self.densify_scale_threshold, size_limit, None if bb is None else self._box_host[1])   # the box on the host: read once
+        split_noise = torch.randn((P, 2, 3), device=dev)
+        box_noise = torch.randn((P, 2, 2, 3), device=dev) if (rule.size_limit and rule.has_box) else None
+        pr = self._params()
+        states = {n: self.optimizer.state.get(p) for n, p in pr.items()}
+        have = [n for n, st in states.items() if st is not None and "exp_avg" in st]
+        if have and len(have) != len(pr):
+            raise dn.DensifyError(f"fused_densify: the groups {have} have Adam moments and the others none")
+        moments = {n: (states[n]["exp_avg"], states[n]["exp_avg_sq"]) for n in pr} if have else None
+        res = dn.densify({n: p.detach() for n, p in pr.items()}, moments, self.xyz_gradient_accum, self.denom, rule, split_noise, box_noise)
+        self._rewrite(lambda n, t: res.groups[n], lambda n, m: None)
+        if moments is not None:
+            for g in self.optimizer.param_groups:
+                st = self.optimizer.state[g["params"][0]]
+                st["exp_avg"], st["exp_avg_sq"] = res.moments[g["name"]]
+        z = torch.zeros((3, res.P_new), device=dev)                             # one fill for the three statistics
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = z[0].unsqueeze(1), z[1].unsqueeze(1), z[2]
+        return res.info
 
     def _inside_box(self, n_samples: int) -> torch.Tensor:
         """Gaussians whose random samples all fall into the actor's tracking box (gaussian_model.py:381-404)."""
@@ -345,17 +384,20 @@ class GaussianScene:
         begin = 0
         for g in self.gaussians_assets:
             n = g._xyz.shape[0]
-            grads, touched = mean_grads[begin:begin + n], (accum_weights[begin:begin + n] > 0).reshape(-1)
+            fused_stats = bool(getattr(opt, "fused_densify", False)) and getattr(g, "fused_densify", False)
+            sparse = getattr(opt, "sparse_adam", False)
+            grads, weights = mean_grads[begin:begin + n], accum_weights[begin:begin + n]
+            touched = (weights > 0).reshape(-1) if (sparse or not fused_stats) else None      # the fused statistics read the weights themselves
             begin += n
             if iteration < opt.densify_until_iter:
-                g.add_densification_stats(grads, touched)
+                g.add_densification_stats(grads, weights if fused_stats else touched)
                 if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
                     info = g.densify_and_prune(opt, 20 if iteration > opt.opacity_reset_interval else None)
                     tot = [a + b for a, b in zip(tot, info)]
                 if iteration % opt.opacity_reset_interval == 0:
                     g.reset_opacity()
             if iteration < opt.iterations:
-                if getattr(opt, "sparse_adam", False):
+                if sparse:
                     g.optimizer.step(rows=None if (g.bounding_box is not None and opt.lambda_reg != 0) else touched)
                 else:
                     g.optimizer.step()

@@ -11,7 +11,9 @@ on this scene's coherent frame and on independent random ranges (the degenerate 
 (fused=True, the default), lidar_rt_amd.optim.GaussianAdam (--fused-adam) and GaussianAdam on the rows the frame hit (--fused-adam --sparse-adam);
 then, profiled in a pass of its own, the GPU kernel time and the launch count of the optimizer part alone (the steps of all assets on the
 gradients of one real backward), and the measured share of touched rows.  S1M by default; --actors: the kitti360_dynamic shape (500 k background
-Gaussians + 8 actors x 8 k with tracking boxes, 66 x 1030 rays), where sparse mode steps the boxed actors densely (lambda_reg != 0)."""
+Gaussians + 8 actors x 8 k with tracking boxes, 66 x 1030 rays), where sparse mode steps the boxed actors densely (lambda_reg != 0).
+--compare-densify: the same alternating windows for the densification statistics of an iteration, the PyTorch ops against the fused operator
+(--fused-densify, lidar_rt_amd.densify.densify_stats), on S1M, in iterations without a densification event (tools/bench_densify.py times the event)."""
 import os, sys, time, types
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
@@ -113,8 +115,58 @@ def compare_adam():
     print("| optimizer part, share of the iteration's wall time (GPU time / iteration) | " + " | ".join(f"{p[0] / 10 / statistics.median(v):.1f} %" for p, v in zip(part, ms)) + " |")
 
 
+def compare_densify():
+    import statistics
+    t = lambda a: torch.as_tensor(a, device=dev)
+    runs = max(5, int(os.environ.get("RUNS", "7")))
+    bg = torch.tensor([0.0, 0.0, 1.0], device=dev)
+    s1, ro, rd = scenes.s1m()
+    op = s1["opacities"]
+
+    def mk(noise):
+        r = np.random.default_rng(1)
+        a = training.GaussianAsset.from_tensors(t(s1["means"] + noise * r.normal(size=s1["means"].shape).astype(np.float32)), t(s1["shs"][:, :1]), t(s1["shs"][:, 1:]),
+                                                t(np.log(s1["scales"])), t(s1["rotations"]), t(np.log(op / (1 - op))), extent=60.0)
+        a.active_sh_degree = 3
+        return a
+    base = training.default_options()
+    base.densify_from_iter = 10 ** 9                               # statistics in every iteration, no event
+    args = types.SimpleNamespace(dynamic=False, opt=base, pipe=types.SimpleNamespace())
+    frames = training.RangeFrames()
+    with torch.no_grad():
+        pk = raytracing(0, [mk(0.0)], (t(ro), t(rd), t(ro[0, 0])), bg, args)
+    frames.add_frame(0, t(ro), t(rd), pk["depth"].squeeze(-1).detach(), pk["intensity"].squeeze(-1).detach(), pk["raydrop"].squeeze(-1) < 0.6)
+    settings = (("PyTorch statistics (default)", {}), ("fused statistics (--fused-densify)", {"fused_densify": True}))
+    opts, scs = [], []
+    for _, kw in settings:
+        o = types.SimpleNamespace(**vars(base))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        sc_ = training.GaussianScene([mk(0.02)]); sc_.training_setup(o)
+        opts.append(o); scs.append(sc_)
+    it = 0
+    for k in range(2):
+        for _ in range(3):
+            it += 1; training.training_step(scs[k], frames, 0, it, opts[k], bg)
+    ms = [[], []]
+    for _ in range(runs):
+        for k in range(2):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(10):
+                it += 1; training.training_step(scs[k], frames, 0, it, opts[k], bg)
+            torch.cuda.synchronize(); ms[k].append((time.perf_counter() - t0) / 10 * 1e3)
+    print(f"S1M: {s1['means'].shape[0]} Gaussians, one asset; {ro.shape[0]} x {ro.shape[1]} rays; {runs} alternating windows of 10 iterations, no densification event")
+    print("| | " + " | ".join(n for n, _ in settings) + " |")
+    print("|---|---:|---:|")
+    f = lambda v: f"{statistics.median(v):.3f} (min {min(v):.3f}, max {max(v):.3f})"
+    print("| training iteration, ms wall | " + " | ".join(f(v) for v in ms) + " |")
+
+
 if "--compare-adam" in sys.argv:
     compare_adam()
+    sys.exit(0)
+if "--compare-densify" in sys.argv:
+    compare_densify()
     sys.exit(0)
 sc, ro, rd = scenes.s1m()
 t = lambda a: torch.as_tensor(a, device=dev)
