@@ -27,6 +27,9 @@
 * ``csrc/liblrt_densify.so`` -- the fused densify-and-prune of an asset (``csrc/lrt_densify.hip``, C ABI ``include/lrt_densify.h``): a seventh product
   library on the same pattern.  Loaded by ``lidar_rt_amd.densify``.
 
+* ``csrc/liblrt_project.so`` -- the range-image projection of point clouds (``csrc/lrt_project.hip``, C ABI ``include/lrt_project.h``): an eighth product
+  library on the same pattern.  Loaded by ``lidar_rt_amd.range_image``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -90,6 +93,11 @@ DENSIFY_LIB = os.path.join(CSRC, "liblrt_densify.so")
 DENSIFY_STAMP = os.path.join(CSRC, "liblrt_densify.srchash")
 DENSIFY_SOURCES = ["lrt_densify.hip"]
 DENSIFY_HEADERS = ["lrt_densify_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_densify.h")]
+# the projection library: once more
+PROJECT_LIB = os.path.join(CSRC, "liblrt_project.so")
+PROJECT_STAMP = os.path.join(CSRC, "liblrt_project.srchash")
+PROJECT_SOURCES = ["lrt_project.hip"]
+PROJECT_HEADERS = ["lrt_project_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_project.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -358,6 +366,46 @@ def build_densify(force: bool = False, verbose: bool = False) -> str:
     return DENSIFY_LIB
 
 
+def project_source_hash() -> str:
+    """source_hash() of the projection library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(PROJECT_SOURCES + PROJECT_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def project_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(PROJECT_LIB):
+        return True
+    try:
+        return open(PROJECT_STAMP).read().strip() != project_source_hash()
+    except OSError:
+        return True
+
+
+def build_project(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_project.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other seven libraries."""
+    if force or project_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", PROJECT_LIB] \
+            + [os.path.join(CSRC, s) for s in PROJECT_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(PROJECT_STAMP, "w") as f:
+            f.write(project_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(PROJECT_LIB)} is up to date (sources {project_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(PROJECT_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return PROJECT_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -459,6 +507,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_metrics(force, verbose)
     build_adam(force, verbose)
     build_densify(force, verbose)
+    build_project(force, verbose)
     return lib
 
 

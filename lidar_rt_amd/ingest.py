@@ -1,0 +1,186 @@
+"""Point clouds into a sequence directory: the converter that ``lidar_rt_amd/sequence.py`` promises, for any source of LiDAR scans.
+
+    ingest_point_clouds(out_dir, clouds, H, W, inclination, data_type="KITTI", sensor2ego=None, max_depth=80.0, test_frames=(),
+                        boxes=None, init=None, device=None, batch=16)
+
+``clouds`` yields ``(frame_id, points (N, 4) [x, y, z, intensity] in the SENSOR frame, sensor2world (4, 4))``.  ``batch`` frames go through
+``range_image.project_points`` per call (``device="cuda"``: the HIP operator; ``"cpu"``: its float64 twin; ``None``: the HIP device when there
+is one); the frames are written with ``sequence.write_sequence`` and ``out_dir/ingest.json`` records the arguments and the six counts of
+every frame (points, invalid, out_of_range, out_of_view, hidden, pixels).  The sequence's ``extent`` is the largest range that became a pixel.
+
+    python -m lidar_rt_amd.ingest --points DIR --poses FILE --out DIR --height 66 --width 1030 --inclination -0.4346 0.0349
+
+``--points DIR`` holds ``<id>.npy`` ``(N, 4)`` or KITTI-style ``<id>.bin`` (float32 quadruples), ids being integers.  ``--poses FILE`` is a ``.npy``
+``(F, 4, 4)`` in the order of the sorted ids, or text rows of an id and 12 or 16 numbers (a 3 x 4 or 4 x 4 sensor-to-world matrix, row-major).
+A frame without a row takes the last earlier pose, as the reference's KITTI loader does (lib/dataloader/kitti_loader/__init__.py:199-242);
+``ingest.json`` records which frames did.  ``--missing-pose error`` refuses instead.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from typing import Iterable, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import range_image, sequence
+
+INGEST_FORMAT = "lidar-rt-amd-ingest/1"
+
+
+def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclination, data_type: str = "KITTI", sensor2ego=None, max_depth: float = 80.0,
+                        test_frames: Sequence[int] = (), boxes: Optional[dict] = None, init: Optional[dict] = None, device=None, batch: int = 16,
+                        wrap: bool = True, notes: Optional[dict] = None) -> dict:
+    """See the module text.  ``wrap``: ``range_image.project_points``'s; ``notes``: further entries for ``ingest.json``.  Returns what ``ingest.json`` holds."""
+    if batch < 1:
+        raise ValueError(f"ingest_point_clouds: batch {batch}")
+    dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
+    inc = [float(x) for x in np.asarray(inclination, np.float64).reshape(-1)]
+    per_frame, extent = [], [0.0]
+
+    def flush(group):
+        sizes = [g[1].shape[0] for g in group]
+        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        pts = np.concatenate([g[1] for g in group]) if group else np.zeros((0, 4), np.float32)
+        img = range_image.project_points(torch.from_numpy(np.ascontiguousarray(pts, np.float32)).to(dev), H, W, inc, offsets=offsets, data_type=data_type,
+                                         sensor2ego=sensor2ego, max_depth=max_depth, wrap=wrap)
+        depth, intensity, mask, counts = (t.cpu().numpy() for t in (img.depth, img.intensity, img.mask, img.counts))
+        for k, (fid, _, s2w) in enumerate(group):
+            per_frame.append({"id": int(fid), **{n: int(v) for n, v in zip(range_image.COUNT_NAMES, counts[k])}})
+            if mask[k].any():
+                extent[0] = max(extent[0], float(depth[k].max()))
+            yield {"id": int(fid), "depth": depth[k], "intensity": intensity[k], "mask": mask[k], "inclination": inc, "sensor2world": s2w}
+
+    def frames():
+        group = []
+        for fid, pts, s2w in clouds:
+            pts = np.asarray(pts.detach().cpu() if torch.is_tensor(pts) else pts)
+            if pts.ndim != 2 or pts.shape[1] not in (3, 4):
+                raise ValueError(f"ingest_point_clouds: frame {fid}: points must be (N, 4) or (N, 3), they are {pts.shape}")
+            if pts.shape[1] == 3:
+                pts = np.concatenate([pts, np.zeros((pts.shape[0], 1), pts.dtype)], 1)
+            group.append((fid, pts.astype(np.float32, copy=False), np.asarray(s2w.detach().cpu() if torch.is_tensor(s2w) else s2w, np.float64).reshape(4, 4)))
+            if len(group) == batch:
+                yield from flush(group)
+                group = []
+        if group:
+            yield from flush(group)
+
+    done = list(frames())                                                    # every image first: the extent is known after the last one
+    meta = sequence.write_sequence(out_dir, done, data_type=data_type, extent=extent[0] if extent[0] > 0.0 else 1.0, sensor2ego=sensor2ego, boxes=boxes, init=init,
+                                   test_frames=test_frames)
+    total = {n: int(sum(f[n] for f in per_frame)) for n in range_image.COUNT_NAMES}
+    report = {"format": INGEST_FORMAT, "height": int(H), "width": int(W), "inclination": inc, "data_type": data_type,
+              "sensor2ego": None if sensor2ego is None else np.asarray(sensor2ego, np.float64).reshape(4, 4).tolist(), "max_depth": float(max_depth),
+              "wrap": bool(wrap), "batch": int(batch), "device": dev.type, "extent": meta["extent"], "frames": per_frame, "total": total, **(notes or {})}
+    with open(os.path.join(out_dir, "ingest.json"), "w") as f:
+        json.dump(report, f, indent=1)
+    return report
+
+
+# ---- the command line ------------------------------------------------------------------------------------------------------------------------------------
+
+def read_points(path: str) -> np.ndarray:
+    if path.endswith(".npy"):
+        a = np.load(path)
+        if a.ndim != 2 or a.shape[1] not in (3, 4):
+            raise ValueError(f"{path}: (N, 4) or (N, 3) expected, the array is {a.shape}")
+        return a
+    raw = np.fromfile(path, dtype=np.float32)
+    if raw.size % 4:
+        raise ValueError(f"{path}: {raw.size} float32 values are not quadruples")
+    return raw.reshape(-1, 4)
+
+
+def list_points(folder: str):
+    """[(id, path)] sorted by id; ``<id>.npy`` wins over ``<id>.bin``."""
+    found = {}
+    for fn in sorted(os.listdir(folder)):
+        stem, ext = os.path.splitext(fn)
+        if ext in (".npy", ".bin") and stem.lstrip("-").isdigit():
+            if int(stem) not in found or ext == ".npy":
+                found[int(stem)] = os.path.join(folder, fn)
+    if not found:
+        raise ValueError(f"{folder}: no <id>.npy or <id>.bin file")
+    return sorted(found.items())
+
+
+def read_poses(path: str, ids: Sequence[int]) -> dict:
+    """{id: (4, 4) float64} for the ids that have a pose."""
+    if path.endswith(".npy"):
+        a = np.load(path).astype(np.float64)
+        if a.ndim != 3 or a.shape != (len(ids), 4, 4):
+            raise ValueError(f"{path}: ({len(ids)}, 4, 4) expected for {len(ids)} frames, the array is {a.shape}")
+        return {i: a[k] for k, i in enumerate(ids)}
+    poses = {}
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            t = line.split()
+            if not t or t[0].startswith("#"):
+                continue
+            if len(t) not in (13, 17):
+                raise ValueError(f"{path}:{ln}: an id and 12 or 16 numbers expected, {len(t)} fields found")
+            m = np.eye(4)
+            m.reshape(-1)[:len(t) - 1] = [float(x) for x in t[1:]]
+            poses[int(float(t[0]))] = m
+    return poses
+
+
+def matrix_file(path: str) -> np.ndarray:
+    a = np.load(path) if path.endswith(".npy") else np.loadtxt(path)
+    a = np.asarray(a, np.float64).reshape(-1)
+    if a.size == 12:
+        a = np.concatenate([a, [0, 0, 0, 1]])
+    if a.size != 16:
+        raise ValueError(f"{path}: a 3 x 4 or 4 x 4 matrix expected")
+    return a.reshape(4, 4)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m lidar_rt_amd.ingest", description="Project point clouds into range images and write a sequence directory.")
+    ap.add_argument("--points", required=True, help="directory of <id>.npy (N, 4) or KITTI-style <id>.bin float32 quadruples, points in the sensor frame")
+    ap.add_argument("--poses", required=True, help=".npy (F, 4, 4) in the order of the sorted ids, or text rows: id and 12 or 16 numbers (sensor to world)")
+    ap.add_argument("--out", required=True, help="the sequence directory to write")
+    ap.add_argument("--sensor2ego", help="a 4 x 4 (or 3 x 4) matrix, .npy or text: the yaw of Waymo data")
+    ap.add_argument("--height", type=int, required=True)
+    ap.add_argument("--width", type=int, required=True)
+    g = ap.add_mutually_exclusive_group(required=True)
+    g.add_argument("--inclination", type=float, nargs=2, metavar=("LO", "HI"), help="the two inclination bounds [rad]")
+    g.add_argument("--beams", help="a per-beam inclination table [rad], one value per row: .npy or text")
+    ap.add_argument("--data-type", choices=("KITTI", "Waymo"), default="KITTI")
+    ap.add_argument("--max-depth", type=float, default=80.0)
+    ap.add_argument("--no-wrap", action="store_true", help="drop a column index outside [0, W) as the reference's loader does, instead of wrapping it")
+    ap.add_argument("--test-frames", type=int, nargs="*", default=[])
+    ap.add_argument("--missing-pose", choices=("previous", "error"), default="previous", help="a frame without a pose row: the last earlier pose, or refuse")
+    ap.add_argument("--device", choices=("cpu", "cuda"), default=None)
+    ap.add_argument("--batch", type=int, default=16)
+    a = ap.parse_args(argv)
+    files = list_points(a.points)
+    ids = [i for i, _ in files]
+    poses = read_poses(a.poses, ids)
+    inc = list(a.inclination) if a.inclination else (np.load(a.beams) if a.beams.endswith(".npy") else np.loadtxt(a.beams)).reshape(-1).tolist()
+    borrowed, use, last = {}, {}, None
+    for i in ids:
+        if i in poses:
+            last = i
+        elif a.missing_pose == "error" or last is None:
+            print(f"ingest: frame {i} has no pose" + ("" if a.missing_pose == "error" else " and no earlier frame has one"), file=sys.stderr)
+            return 2
+        else:
+            borrowed[str(i)] = last
+        use[i] = poses[last]
+    clouds = ((i, read_points(p), use[i]) for i, p in files)
+    rep = ingest_point_clouds(a.out, clouds, a.height, a.width, inc, data_type=a.data_type, sensor2ego=matrix_file(a.sensor2ego) if a.sensor2ego else None,
+                              max_depth=a.max_depth, test_frames=a.test_frames, device=a.device, batch=a.batch, wrap=not a.no_wrap,
+                              notes={"pose_taken_from": borrowed})
+    t = rep["total"]
+    print(f"ingest: {len(ids)} frames, {t['points']} points -> {t['pixels']} pixels ({t['hidden']} hidden, {t['out_of_view']} out of view, "
+          f"{t['out_of_range']} out of range, {t['invalid']} invalid); {len(borrowed)} frames took an earlier pose; wrote {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
