@@ -30,6 +30,9 @@
 * ``csrc/liblrt_project.so`` -- the range-image projection of point clouds (``csrc/lrt_project.hip``, C ABI ``include/lrt_project.h``): an eighth product
   library on the same pattern.  Loaded by ``lidar_rt_amd.range_image``.
 
+* ``csrc/liblrt_sweep.so`` -- the sweep rays of a moving sensor and their pose and twist gradients (``csrc/lrt_sweep.hip``, C ABI ``include/lrt_sweep.h``):
+  a ninth product library on the same pattern.  Loaded by ``lidar_rt_amd.sweep``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -98,6 +101,11 @@ PROJECT_LIB = os.path.join(CSRC, "liblrt_project.so")
 PROJECT_STAMP = os.path.join(CSRC, "liblrt_project.srchash")
 PROJECT_SOURCES = ["lrt_project.hip"]
 PROJECT_HEADERS = ["lrt_project_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_project.h")]
+# the sweep-ray library: once more
+SWEEP_LIB = os.path.join(CSRC, "liblrt_sweep.so")
+SWEEP_STAMP = os.path.join(CSRC, "liblrt_sweep.srchash")
+SWEEP_SOURCES = ["lrt_sweep.hip"]
+SWEEP_HEADERS = ["lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_sweep.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -406,6 +414,46 @@ def build_project(force: bool = False, verbose: bool = False) -> str:
     return PROJECT_LIB
 
 
+def sweep_source_hash() -> str:
+    """source_hash() of the sweep-ray library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(SWEEP_SOURCES + SWEEP_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def sweep_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(SWEEP_LIB):
+        return True
+    try:
+        return open(SWEEP_STAMP).read().strip() != sweep_source_hash()
+    except OSError:
+        return True
+
+
+def build_sweep(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_sweep.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other eight libraries."""
+    if force or sweep_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", SWEEP_LIB] \
+            + [os.path.join(CSRC, s) for s in SWEEP_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(SWEEP_STAMP, "w") as f:
+            f.write(sweep_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(SWEEP_LIB)} is up to date (sources {sweep_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(SWEEP_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return SWEEP_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -508,6 +556,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_adam(force, verbose)
     build_densify(force, verbose)
     build_project(force, verbose)
+    build_sweep(force, verbose)
     return lib
 
 

@@ -23,7 +23,8 @@ def run(args) -> dict:
         raise SystemExit("lidar_rt_amd.evaluate needs a HIP device (there is no CPU path)")
     dev = torch.device("cuda", args.device)
     torch.cuda.set_device(dev)
-    seq = sequence.load_sequence(args.data, dev)
+    seq = sequence.load_sequence(args.data, dev, sweep=getattr(args, "sweep", "off"), sweep_fraction=getattr(args, "sweep_fraction", 1.0),
+                                 sweep_ref=getattr(args, "sweep_ref", 0.5), sweep_direction=getattr(args, "sweep_direction", "cw"))
     opt = training.default_options()
     scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed)
     scene.training_setup(opt)
@@ -59,6 +60,11 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--boxes", default=None, help="refined actor boxes (boxes<it>.pth of python -m lidar_rt_amd.train --refine-boxes) to render with")
     ap.add_argument("--fused-metrics", action="store_true", help="every frame's figures from the fused HIP operator (lidar_rt_amd.metrics) instead of the PyTorch expressions")
+    ap.add_argument("--sweep", choices=("off", "stored", "poses"), default="off", help="render with one pose per column (lidar_rt_amd.sweep), as python -m lidar_rt_amd.train "
+                    "--sweep: stored = each frame's twist from its file, poses = twists derived from consecutive sensor poses")
+    ap.add_argument("--sweep-ref", type=float, default=0.5, help="--sweep: the part of the sweep at which a frame's pose holds")
+    ap.add_argument("--sweep-direction", choices=("cw", "ccw"), default="cw", help="--sweep: cw = time rises with the column index")
+    ap.add_argument("--sweep-fraction", type=float, default=1.0, help="--sweep poses: the part of the time between two consecutive frame ids that one sweep takes")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     args = ap.parse_args(argv)
     res = run(args)

@@ -33,8 +33,10 @@ INGEST_FORMAT = "lidar-rt-amd-ingest/1"
 
 def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclination, data_type: str = "KITTI", sensor2ego=None, max_depth: float = 80.0,
                         test_frames: Sequence[int] = (), boxes: Optional[dict] = None, init: Optional[dict] = None, device=None, batch: int = 16,
-                        wrap: bool = True, notes: Optional[dict] = None) -> dict:
-    """See the module text.  ``wrap``: ``range_image.project_points``'s; ``notes``: further entries for ``ingest.json``.  Returns what ``ingest.json`` holds."""
+                        wrap: bool = True, notes: Optional[dict] = None, twists: Optional[dict] = None) -> dict:
+    """See the module text.  ``wrap``: ``range_image.project_points``'s; ``notes``: further entries for ``ingest.json``; ``twists``: {id: (6,)} the
+    sensor's motion over each frame's sweep (``sweep.twists_from_poses``), stored with the frame for ``load_sequence(..., sweep="stored")`` -- the
+    projection itself is not changed by it.  Returns what ``ingest.json`` holds."""
     if batch < 1:
         raise ValueError(f"ingest_point_clouds: batch {batch}")
     dev = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
@@ -52,7 +54,12 @@ def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclinat
             per_frame.append({"id": int(fid), **{n: int(v) for n, v in zip(range_image.COUNT_NAMES, counts[k])}})
             if mask[k].any():
                 extent[0] = max(extent[0], float(depth[k].max()))
-            yield {"id": int(fid), "depth": depth[k], "intensity": intensity[k], "mask": mask[k], "inclination": inc, "sensor2world": s2w}
+            fr = {"id": int(fid), "depth": depth[k], "intensity": intensity[k], "mask": mask[k], "inclination": inc, "sensor2world": s2w}
+            if twists is not None:
+                if int(fid) not in twists:
+                    raise ValueError(f"ingest_point_clouds: frame {fid} has no twist")
+                fr["twist"] = np.asarray(twists[int(fid)], np.float64).reshape(6)
+            yield fr
 
     def frames():
         group = []
@@ -155,6 +162,9 @@ def main(argv=None) -> int:
     ap.add_argument("--no-wrap", action="store_true", help="drop a column index outside [0, W) as the reference's loader does, instead of wrapping it")
     ap.add_argument("--test-frames", type=int, nargs="*", default=[])
     ap.add_argument("--missing-pose", choices=("previous", "error"), default="previous", help="a frame without a pose row: the last earlier pose, or refuse")
+    ap.add_argument("--sweep", action="store_true", help="also store every frame's twist -- the sensor's motion over one sweep, derived from consecutive poses "
+                    "(lidar_rt_amd.sweep.twists_from_poses) -- for train / evaluate --sweep stored")
+    ap.add_argument("--sweep-fraction", type=float, default=1.0, help="--sweep: the part of the time between two consecutive frame ids that one sweep takes")
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None)
     ap.add_argument("--batch", type=int, default=16)
     a = ap.parse_args(argv)
@@ -172,10 +182,18 @@ def main(argv=None) -> int:
         else:
             borrowed[str(i)] = last
         use[i] = poses[last]
+    twists = None
+    if a.sweep:
+        from . import sweep
+        try:
+            twists = sweep.twists_from_poses(use, a.sweep_fraction)
+        except sweep.SweepError as e:
+            print(f"ingest: --sweep: {e}", file=sys.stderr)
+            return 2
     clouds = ((i, read_points(p), use[i]) for i, p in files)
     rep = ingest_point_clouds(a.out, clouds, a.height, a.width, inc, data_type=a.data_type, sensor2ego=matrix_file(a.sensor2ego) if a.sensor2ego else None,
                               max_depth=a.max_depth, test_frames=a.test_frames, device=a.device, batch=a.batch, wrap=not a.no_wrap,
-                              notes={"pose_taken_from": borrowed})
+                              notes={"pose_taken_from": borrowed, **({"sweep_fraction": float(a.sweep_fraction)} if a.sweep else {})}, twists=twists)
     t = rep["total"]
     print(f"ingest: {len(ids)} frames, {t['points']} points -> {t['pixels']} pixels ({t['hidden']} hidden, {t['out_of_view']} out of view, "
           f"{t['out_of_range']} out of range, {t['invalid']} invalid); {len(borrowed)} frames took an earlier pose; wrote {a.out}")

@@ -5,6 +5,10 @@
 ``loss.backward()`` carries dL/dray_o and dL/dray_d from the tracer back to xi.  The object is duck-typed as a sensor for
 ``renderer.raytracing`` (``get_range_rays``, ``sensor_center``, ``inverse_projection_with_range``, the ground-truth accessors of
 ``frames``) and brings its own Adam optimiser with separate translation / rotation learning rates (``step()`` / ``zero_grad()``).
+
+A frame with sweep rays (``RangeFrames.sweep_meta``: a moving sensor, one pose per column) gets its rays from
+``sweep.sweep_rays(sensor2world @ Exp(xi), twist, ...)`` -- the fused operator, four launches forward and backward instead of the torch
+expression's dozens.  ``refine_twist=True`` makes those frames' twists parameters too, with learning rates of their own.
 """
 from __future__ import annotations
 
@@ -40,7 +44,8 @@ def se3_exp(xi: torch.Tensor) -> torch.Tensor:
 
 
 class SensorPoses:
-    def __init__(self, frames, frame_ids: Optional[Iterable[int]] = None, lr_trans: float = 1e-3, lr_rot: float = 1e-3):
+    def __init__(self, frames, frame_ids: Optional[Iterable[int]] = None, lr_trans: float = 1e-3, lr_rot: float = 1e-3, refine_twist: bool = False,
+                 lr_twist_trans: Optional[float] = None, lr_twist_rot: Optional[float] = None):
         meta = getattr(frames, "pose_meta", {})
         ids = list(frame_ids) if frame_ids is not None else list(frames.train_frames)
         for f in ids:
@@ -51,8 +56,25 @@ class SensorPoses:
         self.frame_ids = ids
         dev = frames.depth[ids[0]].device if ids else torch.device("cpu")
         self.xi: Dict[int, torch.nn.Parameter] = {f: torch.nn.Parameter(torch.zeros(6, dtype=torch.float32, device=dev)) for f in ids}
-        self.optimizer = torch.optim.Adam([{"params": list(self.xi.values()), "lr": 1.0, "name": "xi"}], betas=(0.9, 0.999), eps=1e-15)
+        groups = [{"params": list(self.xi.values()), "lr": 1.0, "name": "xi"}]
+        # frames with sweep rays (RangeFrames.sweep_meta): their motion over the sweep, a parameter too under refine_twist
+        sweep_meta = getattr(frames, "sweep_meta", {})
+        self.refine_twist = bool(refine_twist)
+        self.twist: Dict[int, torch.Tensor] = {}
+        self._sweep_args: Dict[int, tuple] = {}               # per sweep frame: what sweep_rays needs besides pose and twist, made once
+        for f in ids:
+            if f in sweep_meta:
+                tw, tau = sweep_meta[f]
+                tw = tw.detach().to(device=dev, dtype=torch.float32).clone()
+                self.twist[f] = torch.nn.Parameter(tw) if self.refine_twist else tw
+        if self.refine_twist:
+            if not self.twist:
+                raise ValueError("SensorPoses: refine_twist needs frames with sweep rays (add_range_image(..., twist=...)); none of the frames has a twist")
+            groups.append({"params": list(self.twist.values()), "lr": 1.0, "name": "twist"})
+        self.optimizer = torch.optim.Adam(groups, betas=(0.9, 0.999), eps=1e-15)
         self.lr_trans, self.lr_rot = float(lr_trans), float(lr_rot)
+        self.lr_twist_trans = float(lr_trans if lr_twist_trans is None else lr_twist_trans)
+        self.lr_twist_rot = float(lr_rot if lr_twist_rot is None else lr_twist_rot)
 
     # ---- the corrected poses ---------------------------------------------------------------------------------------------------
     def sensor2world(self, frame) -> torch.Tensor:
@@ -60,9 +82,28 @@ class SensorPoses:
         inc, s2w, _, _ = self.frames.pose_meta[frame]
         return s2w.to(torch.float32) @ se3_exp(self.xi[frame])
 
+    def _sweep(self, frame):
+        a = self._sweep_args.get(frame)
+        if a is None:
+            inc, s2w, data_type, s2e = self.frames.pose_meta[frame]
+            H, W = self.frames.depth[frame].shape[:2]
+            dev = s2w.device
+            s2e_host = None
+            if data_type == "Waymo" and s2e is not None:
+                s2e_host = torch.as_tensor(s2e).detach().to("cpu", torch.float32)       # read back once, not per iteration
+            inc = [-float(inc), float(inc)] if isinstance(inc, (int, float)) else inc
+            inc_t = torch.as_tensor(inc, dtype=torch.float32).reshape(-1).to(dev)
+            a = (H, W, inc_t, data_type, s2e_host, self.frames.sweep_meta[frame][1].to(device=dev, dtype=torch.float32))
+            self._sweep_args[frame] = a
+        return a
+
     def get_range_rays(self, frame):
         inc, s2w, data_type, s2e = self.frames.pose_meta[frame]
         H, W = self.frames.depth[frame].shape[:2]
+        if frame in self.twist:                                   # a moving sensor: one pose per column, through the fused operator
+            from . import sweep
+            H, W, inc_t, data_type, s2e_host, tau = self._sweep(frame)
+            return sweep.sweep_rays(self.sensor2world(frame), self.twist[frame], H, W, inc_t, data_type, s2e_host, tau=tau)
         return self.frames.range_rays(H, W, inc, self.sensor2world(frame), data_type, s2e)
 
     @property
@@ -90,23 +131,51 @@ class SensorPoses:
     @torch.no_grad()
     def step(self):
         """One Adam step; the translation (rho) and rotation (phi) parts of xi have their own learning rates (Adam's update is
-        elementwise, so scaling a unit-rate step per component is exactly two learning rates)."""
-        before = {f: x.detach().clone() for f, x in self.xi.items()}
+        elementwise, so scaling a unit-rate step per component is exactly two learning rates), and so have the twists' under refine_twist."""
+        params = dict(self.xi)
+        twists = {f: x for f, x in self.twist.items()} if self.refine_twist else {}
+        before = {f: x.detach().clone() for f, x in params.items()}
+        before_tw = {f: x.detach().clone() for f, x in twists.items()}
         self.optimizer.step()
-        scale = torch.tensor([self.lr_trans] * 3 + [self.lr_rot] * 3, device=next(iter(self.xi.values())).device)
-        for f, x in self.xi.items():
+        dev = next(iter(self.xi.values())).device
+        scale = torch.tensor([self.lr_trans] * 3 + [self.lr_rot] * 3, device=dev)
+        for f, x in params.items():
             x.copy_(before[f] + (x - before[f]) * scale)
+        if twists:
+            scale_tw = torch.tensor([self.lr_twist_trans] * 3 + [self.lr_twist_rot] * 3, device=dev)
+            for f, x in twists.items():
+                x.copy_(before_tw[f] + (x - before_tw[f]) * scale_tw)
 
     def state_dict(self):
-        return {"xi": {f: x.detach().cpu() for f, x in self.xi.items()}, "optimizer": self.optimizer.state_dict(),
-                "lr_trans": self.lr_trans, "lr_rot": self.lr_rot}
+        sd = {"xi": {f: x.detach().cpu() for f, x in self.xi.items()}, "optimizer": self.optimizer.state_dict(),
+              "lr_trans": self.lr_trans, "lr_rot": self.lr_rot}
+        if self.twist:
+            sd.update(twist={f: x.detach().cpu() for f, x in self.twist.items()}, refine_twist=self.refine_twist,
+                      lr_twist_trans=self.lr_twist_trans, lr_twist_rot=self.lr_twist_rot)
+        return sd
 
     def load_state_dict(self, sd):
         with torch.no_grad():
             for f, x in sd["xi"].items():
                 self.xi[f].copy_(x.to(self.xi[f].device))
-        self.optimizer.load_state_dict(sd["optimizer"])
+            for f, x in sd.get("twist", {}).items():                    # a state dict from before the twists (or of static frames) has none
+                if f in self.twist:
+                    self.twist[f].copy_(x.to(self.twist[f].device))
+        groups = len(sd["optimizer"]["param_groups"])
+        if groups == len(self.optimizer.param_groups):
+            self.optimizer.load_state_dict(sd["optimizer"])
+        elif groups == 1 and self.refine_twist:
+            # saved without twists: the xi group's moments are restored, the twists start fresh
+            xi_only = torch.optim.Adam([self.optimizer.param_groups[0]], betas=(0.9, 0.999), eps=1e-15)
+            xi_only.load_state_dict(sd["optimizer"])
+            for p in self.optimizer.param_groups[0]["params"]:
+                if p in xi_only.state:
+                    self.optimizer.state[p] = xi_only.state[p]
+        else:
+            raise ValueError(f"SensorPoses: the state dict's optimizer has {groups} parameter groups, this one {len(self.optimizer.param_groups)}")
         self.lr_trans, self.lr_rot = float(sd["lr_trans"]), float(sd["lr_rot"])
+        self.lr_twist_trans = float(sd.get("lr_twist_trans", self.lr_twist_trans))
+        self.lr_twist_rot = float(sd.get("lr_twist_rot", self.lr_twist_rot))
 
 
 class _Centers:

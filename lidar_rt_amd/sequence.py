@@ -68,8 +68,17 @@ def write_sequence(root: str, frames: Iterable[dict], data_type: str = "KITTI", 
         inc = npy(fr["inclination"]).reshape(-1)
         if inc.size not in (2, H):
             raise ValueError(f"frame {fr['id']}: inclination must hold 2 bounds or {H} per-beam angles, got {inc.size}")
+        extra = {}
+        if fr.get("twist") is not None:                              # a moving sensor: written only when given
+            extra["twist"] = npy(fr["twist"]).reshape(6)
+        if fr.get("tau") is not None:
+            if "twist" not in extra:
+                raise ValueError(f"frame {fr['id']}: column times without a twist")
+            extra["tau"] = npy(fr["tau"]).reshape(-1)
+            if extra["tau"].size != W:
+                raise ValueError(f"frame {fr['id']}: tau must hold {W} column times, got {extra['tau'].size}")
         np.savez(_frame_path(root, fr["id"]), depth=d, intensity=npy(fr["intensity"]).reshape(H, W), mask=npy(fr["mask"], np.bool_).reshape(H, W),
-                 inclination=inc, sensor2world=npy(fr["sensor2world"]).reshape(4, 4))
+                 inclination=inc, sensor2world=npy(fr["sensor2world"]).reshape(4, 4), **extra)
         ids.append(int(fr["id"]))
     if not ids:
         raise ValueError("a sequence needs at least one frame")
@@ -95,9 +104,37 @@ def write_sequence(root: str, frames: Iterable[dict], data_type: str = "KITTI", 
     return meta
 
 
-def load_sequence(root: str, device="cuda", frames: Optional[Sequence[int]] = None) -> SimpleNamespace:
+SWEEP_MODES = (None, "off", "stored", "poses")
+
+
+def pose_twists(root: str, ids: Sequence[int], sweep_fraction: float = 1.0) -> Dict[int, np.ndarray]:
+    """The sensor's motion over one sweep, per frame, from the sequence's own poses: xi_k = Log(T_k^-1 T_next) * sweep_fraction / (id gap) over
+    ALL frames ``ids`` sorted by id (``sweep_fraction``: the part of the time between two consecutive ids that one sweep takes); the last
+    frame takes the previous interval's.  A single frame has no neighbour and is refused."""
+    from . import sweep
+    ids = sorted(int(i) for i in ids)
+    if len(ids) < 2:
+        raise ValueError(f"{root}: twists from poses need at least two frames (the sequence has {len(ids)})")
+    T = {}
+    for fid in ids:
+        p = _frame_path(root, fid)
+        if not os.path.exists(p):
+            raise FileNotFoundError(f"{root}: meta.json lists frame {fid} but {p} is missing")
+        T[fid] = np.load(p)["sensor2world"].astype(np.float64).reshape(4, 4)
+    return sweep.twists_from_poses(T, sweep_fraction)
+
+
+def load_sequence(root: str, device="cuda", frames: Optional[Sequence[int]] = None, sweep: Optional[str] = None, sweep_fraction: float = 1.0,
+                  sweep_ref: float = 0.5, sweep_direction: str = "cw") -> SimpleNamespace:
     """-> namespace(meta, frames: RangeFrames, boxes: [TrackingBox], init: {name: {points, intensity, normals}}, train_frames, test_frames).
-    The ray grids are derived from inclination + pose like ``LiDARSensor.get_range_rays`` does (RangeFrames.range_rays)."""
+    The ray grids are derived from inclination + pose like ``LiDARSensor.get_range_rays`` does (RangeFrames.range_rays).
+
+    ``sweep``: None (or "off") -- one pose per frame, as ever; "stored" -- every frame's ``twist`` (and ``tau``, else
+    ``sweep.column_times(W, sweep_ref, sweep_direction)``) from its file, a frame without one is refused; "poses" -- the twists of
+    ``pose_twists(root, meta["frames"], sweep_fraction)``.  With a sweep the rays are ``sweep.sweep_rays``: one pose per column."""
+    if sweep not in SWEEP_MODES:
+        raise ValueError(f"load_sequence: sweep {sweep!r} (None, 'off', 'stored' or 'poses')")
+    sweep = None if sweep == "off" else sweep
     with open(os.path.join(root, "meta.json")) as f:
         meta = json.load(f)
     if meta.get("format") != FORMAT:
@@ -106,6 +143,10 @@ def load_sequence(root: str, device="cuda", frames: Optional[Sequence[int]] = No
     rf = RangeFrames()
     s2e = None if meta.get("sensor2ego") is None else torch.tensor(meta["sensor2ego"], dtype=torch.float32, device=dev)
     want = list(meta["frames"]) if frames is None else [int(f) for f in frames]
+    twists = pose_twists(root, meta["frames"], sweep_fraction) if sweep == "poses" else {}
+    if sweep is not None:
+        from . import sweep as sweep_mod
+        default_tau = sweep_mod.column_times(int(meta["width"]), sweep_ref, sweep_direction)
     for fid in want:
         p = _frame_path(root, fid)
         if not os.path.exists(p):
@@ -115,8 +156,17 @@ def load_sequence(root: str, device="cuda", frames: Optional[Sequence[int]] = No
         if tuple(d.shape) != (meta["height"], meta["width"]):
             raise ValueError(f"{p}: range image {tuple(d.shape)} differs from meta.json's {(meta['height'], meta['width'])}")
         inc = [float(x) for x in z["inclination"].reshape(-1)]
+        twist = tau = None
+        if sweep == "stored":
+            if "twist" not in z.files:
+                raise ValueError(f"{p}: no stored twist (sweep='stored' needs one per frame; sweep='poses' derives them from the poses)")
+            twist = torch.as_tensor(z["twist"].astype(np.float32))
+            tau = torch.as_tensor(z["tau"].astype(np.float32)) if "tau" in z.files else default_tau
+        elif sweep == "poses":
+            twist, tau = torch.as_tensor(twists[fid].astype(np.float32)), default_tau
         rf.add_range_image(fid, d, torch.as_tensor(z["intensity"], device=dev), torch.as_tensor(z["mask"], device=dev),
-                           inc if len(inc) > 2 else (inc[0], inc[1]), torch.as_tensor(z["sensor2world"], device=dev), meta["data_type"], s2e)
+                           inc if len(inc) > 2 else (inc[0], inc[1]), torch.as_tensor(z["sensor2world"], device=dev), meta["data_type"], s2e,
+                           **({} if twist is None else {"twist": twist, "tau": tau}))
     boxes: List[TrackingBox] = []
     bp = os.path.join(root, "boxes.npz")
     if os.path.exists(bp):
@@ -137,7 +187,7 @@ def load_sequence(root: str, device="cuda", frames: Optional[Sequence[int]] = No
                 init[fn[:-4]] = {k: torch.as_tensor(z[k], device=dev) for k in z.files}
     test = [t for t in meta.get("test_frames", []) if t in rf.rays]
     train = [f for f in sorted(rf.rays) if f not in set(test)] or sorted(rf.rays)
-    return SimpleNamespace(meta=meta, frames=rf, boxes=boxes, init=init, train_frames=train, test_frames=test, root=root)
+    return SimpleNamespace(meta=meta, frames=rf, boxes=boxes, init=init, train_frames=train, test_frames=test, root=root, sweep=sweep)
 
 
 def scene_from_sequence(seq: SimpleNamespace, max_sh_degree: int = 3, max_points: int = 2_000_000, seed: int = 0, init_from_frames: bool = False,

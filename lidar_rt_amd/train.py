@@ -51,7 +51,9 @@ def run(args) -> dict:
     renderer.deferred_accum = not args.exact_accum       # the loop reads the hit weights after loss.backward() only (train.py:156,219)
     renderer.deterministic = bool(args.deterministic)    # gradient sums in a fixed order, a forward without learnt state: a resumed run repeats the uninterrupted one bit for bit
 
-    seq = sequence.load_sequence(args.data, dev)
+    # --sweep: one pose per column (lidar_rt_amd.sweep); callers that build `args` themselves need not know the switches
+    seq = sequence.load_sequence(args.data, dev, sweep=getattr(args, "sweep", "off"), sweep_fraction=getattr(args, "sweep_fraction", 1.0),
+                                 sweep_ref=getattr(args, "sweep_ref", 0.5), sweep_direction=getattr(args, "sweep_direction", "cw"))
     opt = training.default_options()
     for kv in args.opt:
         k, v = kv.split("=", 1)
@@ -76,7 +78,10 @@ def run(args) -> dict:
     if args.refine_poses:
         # one se(3) correction per training frame, learnt through the tracer's ray gradients (lidar_rt_amd.poses); saved beside each checkpoint
         from .poses import SensorPoses
-        sensor_poses = SensorPoses(seq.frames, seq.train_frames, lr_trans=args.pose_lr_trans, lr_rot=args.pose_lr_rot)
+        # --refine-twist: a moving sensor's twists are parameters too (frames loaded with --sweep carry them)
+        sensor_poses = SensorPoses(seq.frames, seq.train_frames, lr_trans=args.pose_lr_trans, lr_rot=args.pose_lr_rot,
+                                   refine_twist=bool(getattr(args, "refine_twist", False)), lr_twist_trans=getattr(args, "twist_lr_trans", None),
+                                   lr_twist_rot=getattr(args, "twist_lr_rot", None))
     box_poses = None
     if args.refine_boxes:
         # one se(3) correction per (actor, training frame) with a box, learnt through the pose-table gradient of the fused pre-processing
@@ -174,6 +179,15 @@ def main(argv=None) -> int:
                     "ray gradients (lidar_rt_amd.poses); written as poses<it>.pth beside each checkpoint and read back by --resume")
     ap.add_argument("--pose-lr-trans", type=float, default=1e-3, help="--refine-poses: Adam learning rate of the translation part (m)")
     ap.add_argument("--pose-lr-rot", type=float, default=1e-4, help="--refine-poses: Adam learning rate of the rotation part (rad)")
+    ap.add_argument("--sweep", choices=("off", "stored", "poses"), default="off", help="the sensor moves while it turns: every column of a range image gets its own "
+                    "pose (lidar_rt_amd.sweep).  stored: each frame's twist (and column times) from its file; poses: twists derived from consecutive "
+                    "sensor poses; off (the default): one pose per frame")
+    ap.add_argument("--sweep-ref", type=float, default=0.5, help="--sweep: the part of the sweep at which a frame's pose holds (0 = its first column, 0.5 = its middle)")
+    ap.add_argument("--sweep-direction", choices=("cw", "ccw"), default="cw", help="--sweep: cw = time rises with the column index (a clockwise-spinning sensor)")
+    ap.add_argument("--sweep-fraction", type=float, default=1.0, help="--sweep poses: the part of the time between two consecutive frame ids that one sweep takes")
+    ap.add_argument("--refine-twist", action="store_true", help="also learn every frame's twist; needs --refine-poses and a --sweep")
+    ap.add_argument("--twist-lr-trans", type=float, default=1e-3, help="--refine-twist: Adam learning rate of the twists' translation part (m per sweep)")
+    ap.add_argument("--twist-lr-rot", type=float, default=1e-4, help="--refine-twist: Adam learning rate of the twists' rotation part (rad per sweep)")
     ap.add_argument("--refine-boxes", action="store_true", help="also learn a per-frame se(3) correction of every actor's tracking box through the "
                     "pose-table gradient of the fused pre-processing (lidar_rt_amd.actor_poses); written as boxes<it>.pth beside each checkpoint and "
                     "read back by --resume; works with --gpus N")
@@ -188,6 +202,10 @@ def main(argv=None) -> int:
         ap.error("--voxel-size must be positive")
     if args.refine_poses and args.gpus > 1:
         ap.error("--refine-poses needs ray gradients, which azimuth sharding (--gpus > 1) does not provide")
+    if args.refine_twist and not args.refine_poses:               # so --refine-twist is refused with --gpus > 1 too: --refine-poses is, above
+        ap.error("--refine-twist needs --refine-poses (the twists are learnt beside the pose corrections)")
+    if args.refine_twist and args.sweep == "off":
+        ap.error("--refine-twist needs a sweep (--sweep stored or --sweep poses): without one a frame has no twist")
     if args.exact_accum and args.deterministic:
         ap.error("--deterministic takes the hit weights from the backward (the forward's are float atomics): not with --exact-accum")
     if args.out is None:

@@ -417,6 +417,7 @@ class RangeFrames:
         self.mask_index: Dict[int, torch.Tensor] = {}
         self.sensor_center: Dict[int, torch.Tensor] = {}
         self.pose_meta: Dict[int, tuple] = {}     # frames added by add_range_image: (inclination, sensor2world, data_type, sensor2ego) -- poses.SensorPoses
+        self.sweep_meta: Dict[int, tuple] = {}    # frames added with a twist: (twist (6,), tau (W,) float32 on the frame's device) -- lidar_rt_amd.sweep
 
     @staticmethod
     def range_rays(H: int, W: int, inclination, sensor2world: torch.Tensor, data_type: str = "KITTI",
@@ -446,9 +447,22 @@ class RangeFrames:
         o = sensor2world[:3, 3][None, None, :].expand(H, W, 3)
         return o.contiguous(), d.contiguous()
 
-    def add_range_image(self, frame, depth, intensity, mask, inclination, sensor2world, data_type="KITTI", sensor2ego=None):
-        """A frame given as range image + sensor pose (what the reference's loaders put into LiDARSensor)."""
-        o, d = self.range_rays(depth.shape[0], depth.shape[1], inclination, sensor2world, data_type, sensor2ego)
+    def add_range_image(self, frame, depth, intensity, mask, inclination, sensor2world, data_type="KITTI", sensor2ego=None, twist=None, tau=None):
+        """A frame given as range image + sensor pose (what the reference's loaders put into LiDARSensor).  ``twist`` (6,): the sensor moved
+        by Exp(twist) over the sweep, so column w has the pose sensor2world @ Exp(tau[w] twist) (``tau`` (W,): the columns' instants in sweeps,
+        default ``sweep.column_times(W)``); the rays are ``sweep.sweep_rays`` then, one origin per column."""
+        if twist is None:
+            if tau is not None:
+                raise ValueError(f"add_range_image: frame {frame} has column times but no twist")
+            o, d = self.range_rays(depth.shape[0], depth.shape[1], inclination, sensor2world, data_type, sensor2ego)
+        else:
+            from . import sweep
+            dev, W = sensor2world.device, depth.shape[1]
+            twist = torch.as_tensor(twist, dtype=torch.float32).reshape(6).to(dev)
+            tau = (sweep.column_times(W) if tau is None else torch.as_tensor(tau).reshape(-1)).to(device=dev, dtype=torch.float32)
+            with torch.no_grad():
+                o, d = sweep.sweep_rays(sensor2world.to(torch.float32), twist, depth.shape[0], W, inclination, data_type, sensor2ego, tau=tau)
+            self.sweep_meta[frame] = (twist, tau)
         self.add_frame(frame, o, d, depth, intensity, mask)
         self.pose_meta[frame] = (inclination, sensor2world, data_type, sensor2ego)
 

@@ -45,12 +45,16 @@ class _GT:
         return self.xyz if ps is None else self.xyz @ _rotation_matrix(ps[1].reshape(1, 4)).squeeze(0).T + ps[0]
 
 
-def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0", test_every: int = 0):
+def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0", test_every: int = 0, sweep_speed: float = 0.0, hw=None):
+    """``sweep_speed`` V != 0: the sensor moves while it turns -- V metres forward (its x axis) and 0.01 V rad of yaw per sweep; the ground truth is
+    rendered with sweep rays (lidar_rt_amd.sweep: one pose per column, the frame's pose at mid-sweep) and every frame stores its twist.
+    ``hw``: another image size than the dataset's (tests)."""
     dev = torch.device(device)
+    twist = None if not sweep_speed else np.array([sweep_speed, 0.0, 0.0, 0.0, 0.0, 0.01 * sweep_speed], np.float32)
     n = lambda x: max(int(x * scale), 64)
     boxes, actors = None, []
     if shape == "kitti360_dynamic":
-        H, W = scenes.KITTI360_HW
+        H, W = hw or scenes.KITTI360_HW
         bg, act, poses_of, _ = scenes.kitti360_dynamic(P_bg=n(500_000), n_actors=8, per_actor=n(8000))
         data_type, s2e, inc = "KITTI", None, (math.radians(-24.9), math.radians(2.0))
         pose_s = lambda f: scenes.pose_matrix((0.5 * f, 0.0, 0.0), yaw=0.01 * f)
@@ -61,7 +65,7 @@ def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0
         boxes = {"frames": list(range(n_frames)), "translation": tr, "quaternion": qu, "size": size + np.array([[0, 0, 1.8]], np.float32)}
         actors = act
     else:
-        H, W = scenes.WAYMO_HW
+        H, W = hw or scenes.WAYMO_HW
         data_type, s2e, inc = "Waymo", scenes.pose_matrix((1.43, 0.0, 2.18), yaw=0.02), scenes.waymo_inclinations(H)
         pose_s = lambda f: scenes.pose_matrix((0.8 * f, 0.1 * f, 0.45), yaw=0.03 * f + 0.4, pitch=0.01, roll=-0.008)
         if shape == "waymo_static":
@@ -94,15 +98,20 @@ def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0
         with torch.no_grad():
             for f in range(n_frames):
                 s2w = torch.as_tensor(pose_s(f), device=dev)
-                o, d = RangeFrames.range_rays(H, W, [float(x) for x in inc] if len(inc) > 2 else (float(inc[0]), float(inc[1])), s2w, data_type,
-                                              None if s2e is None else torch.as_tensor(s2e, device=dev))
+                inc_f = [float(x) for x in inc] if len(inc) > 2 else (float(inc[0]), float(inc[1]))
+                if twist is None:
+                    o, d = RangeFrames.range_rays(H, W, inc_f, s2w, data_type, None if s2e is None else torch.as_tensor(s2e, device=dev))
+                else:
+                    from lidar_rt_amd import sweep
+                    o, d = sweep.sweep_rays(s2w.to(torch.float32), torch.as_tensor(twist, device=dev), H, W, inc_f, data_type,
+                                            None if s2e is None else torch.as_tensor(s2e, dtype=torch.float32))
                 renderer.tracer_2dgs = renderer.tracer_2dgs or renderer.Tracer()
                 renderer.tracer_2dgs.eval()
                 pkg = renderer.raytracing(f, assets, (o, d, o[0, 0]), torch.tensor([0.0, 0.0, 1.0]), args)
                 drop = pkg["raydrop"].squeeze(-1)
                 mask = (drop < 0.5) & (pkg["depth"].squeeze(-1) > 0.2)
                 frames.append({"id": f, "depth": pkg["depth"].squeeze(-1) * mask, "intensity": pkg["intensity"].squeeze(-1).clamp(0, 1) * mask, "mask": mask,
-                               "inclination": np.asarray(inc, np.float32), "sensor2world": s2w})
+                               "inclination": np.asarray(inc, np.float32), "sensor2world": s2w, **({} if twist is None else {"twist": twist})})
     finally:
         renderer.tracer_2dgs, renderer.use_fused_preprocess, renderer.deferred_accum = old
     test = [f for f in range(n_frames) if test_every and f % test_every == test_every - 1]
@@ -116,5 +125,8 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--test-every", type=int, default=0)
+    ap.add_argument("--sweep-speed", type=float, default=0.0, metavar="V", help="a moving sensor: V metres forward and 0.01 V rad of yaw per sweep; the ground truth "
+                    "is rendered with sweep rays and the twists are stored (train / evaluate --sweep stored)")
+    ap.add_argument("--hw", type=int, nargs=2, default=None, metavar=("H", "W"), help="another image size than the dataset's")
     a = ap.parse_args()
-    print(make(a.shape, a.out, a.frames, a.scale, test_every=a.test_every))
+    print(make(a.shape, a.out, a.frames, a.scale, test_every=a.test_every, sweep_speed=a.sweep_speed, hw=tuple(a.hw) if a.hw else None))
