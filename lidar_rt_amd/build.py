@@ -33,6 +33,9 @@
 * ``csrc/liblrt_sweep.so`` -- the sweep rays of a moving sensor and their pose and twist gradients (``csrc/lrt_sweep.hip``, C ABI ``include/lrt_sweep.h``):
   a ninth product library on the same pattern.  Loaded by ``lidar_rt_amd.sweep``.
 
+* ``csrc/liblrt_refine.so`` -- the inference of the ray-drop refinement network (``csrc/lrt_refine.hip``, C ABI ``include/lrt_refine.h``): a tenth
+  product library on the same pattern.  Loaded by ``lidar_rt_amd.raydrop_refine``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -106,6 +109,11 @@ SWEEP_LIB = os.path.join(CSRC, "liblrt_sweep.so")
 SWEEP_STAMP = os.path.join(CSRC, "liblrt_sweep.srchash")
 SWEEP_SOURCES = ["lrt_sweep.hip"]
 SWEEP_HEADERS = ["lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_sweep.h")]
+# the ray-drop refinement library: once more
+REFINE_LIB = os.path.join(CSRC, "liblrt_refine.so")
+REFINE_STAMP = os.path.join(CSRC, "liblrt_refine.srchash")
+REFINE_SOURCES = ["lrt_refine.hip"]
+REFINE_HEADERS = ["lrt_refine_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_refine.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -454,6 +462,46 @@ def build_sweep(force: bool = False, verbose: bool = False) -> str:
     return SWEEP_LIB
 
 
+def refine_source_hash() -> str:
+    """source_hash() of the ray-drop refinement library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(REFINE_SOURCES + REFINE_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def refine_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(REFINE_LIB):
+        return True
+    try:
+        return open(REFINE_STAMP).read().strip() != refine_source_hash()
+    except OSError:
+        return True
+
+
+def build_refine(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_refine.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other nine libraries."""
+    if force or refine_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", REFINE_LIB] \
+            + [os.path.join(CSRC, s) for s in REFINE_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(REFINE_STAMP, "w") as f:
+            f.write(refine_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(REFINE_LIB)} is up to date (sources {refine_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(REFINE_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return REFINE_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -557,6 +605,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_densify(force, verbose)
     build_project(force, verbose)
     build_sweep(force, verbose)
+    build_refine(force, verbose)
     return lib
 
 

@@ -5,7 +5,9 @@ writes: ``torch.save(([12-tuple per asset], iteration), path)``, gaussian_model.
 Renders the chosen frames forward-only through ``renderer.raytracing`` (no host synchronisation between frames: ``evaluation.render_frames``),
 computes the metric set of eval.py:282-365 (depth / intensity: rmse, mae, medae, ssim, psnr; ray-drop: rmse, accuracy, F1; points: Chamfer distance
 and F-score through the package's own Chamfer operator) and prints ONE JSON object ``{"iteration", "frames", "mean", "per_frame"}``; ``--out`` also
-writes it to a file.  Not reproduced (``evaluation.py``): LPIPS, the U-Net ray-drop refinement, image / point-cloud dumps.
+writes it to a file.  ``--unet PATH`` puts the ray-drop refinement network (``lidar_rt_amd.raydrop_refine``; a ``unet<it>.pth`` of ``python -m
+lidar_rt_amd.train --refine-raydrop`` or the reference's ``unet.pth``) behind every render, as eval.py:129-144 does -- with the stored batch-norm
+statistics and without dropout.  Not reproduced (``evaluation.py``): LPIPS, image / point-cloud dumps.
 """
 from __future__ import annotations
 
@@ -36,14 +38,37 @@ def run(args) -> dict:
         if not seq.boxes:
             raise SystemExit(f"--boxes: {args.data} has no tracking boxes (boxes.npz)")
         ActorPoses.from_state_dict(seq.boxes, torch.load(args.boxes, map_location=dev, weights_only=False)).install(scene.gaussians_assets)
+    refiner = None
+    if getattr(args, "unet", None):
+        refiner = load_refiner(args.unet, dev, spatial=not getattr(args, "unet_no_spatial", False), backend=getattr(args, "unet_backend", None))
     frames = {"test": seq.test_frames or seq.train_frames, "train": seq.train_frames, "all": sorted(set(seq.train_frames) | set(seq.test_frames))}[args.frames]
     if args.max_frames > 0:
         frames = frames[:args.max_frames]
     bg = torch.tensor([0.0, 0.0, 1.0], device=dev)          # the reference's background for (intensity, ray-hit, ray-drop): eval.py:104
     rargs = SimpleNamespace(dynamic=bool(seq.meta.get("dynamic")), opt=SimpleNamespace(use_rayhit=bool(getattr(opt, "use_rayhit", False))), pipe=SimpleNamespace())
     res = evaluation.evaluate(scene.gaussians_assets, seq.frames, frames, bg, rargs, raydrop_ratio=args.raydrop_ratio, use_gt_mask=args.use_gt_mask,
-                              max_depth=args.max_depth, fused=bool(args.fused_metrics))
+                              max_depth=args.max_depth, fused=bool(args.fused_metrics), refiner=refiner)
     return {"iteration": int(iteration), "frames": [int(f) for f in frames], "mean": res["mean"], "per_frame": {str(k): v for k, v in res["frames"].items()}}
+
+
+def load_refiner(path: str, dev, spatial: bool = True, backend=None):
+    """The network of a ``unet*.pth`` (a plain state_dict in the reference's names) on `dev`, packed for the HIP operator; a width that is no
+    multiple of 8 is served by the module itself."""
+    from . import raydrop_refine
+    sd = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(sd, dict) or "inc.conv.weight" not in sd:
+        raise SystemExit(f"--unet: {path} is not a state_dict of the ray-drop refinement network")
+    channels, in_channels = int(sd["inc.conv.weight"].shape[0]), int(sd["inc.conv.weight"].shape[1])
+    if in_channels != (9 if spatial else 3):
+        raise SystemExit(f"--unet: {path} takes {in_channels} input channels ({'without' if spatial else 'with'} --unet-no-spatial: {9 if spatial else 3})")
+    net = raydrop_refine.RaydropUNet(in_channels, channels, 1)
+    net.load_state_dict(sd, strict=True)
+    net = net.to(dev).eval()
+    if channels % 8 != 0:
+        if backend == "hip":
+            raise SystemExit(f"--unet-backend hip: a network of {channels} channels (the operator needs a multiple of 8)")
+        return net
+    return raydrop_refine.pack(net, backend=backend)
 
 
 def main(argv=None) -> int:
@@ -60,6 +85,11 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--boxes", default=None, help="refined actor boxes (boxes<it>.pth of python -m lidar_rt_amd.train --refine-boxes) to render with")
     ap.add_argument("--fused-metrics", action="store_true", help="every frame's figures from the fused HIP operator (lidar_rt_amd.metrics) instead of the PyTorch expressions")
+    ap.add_argument("--unet", default=None, help="state_dict of the ray-drop refinement network (unet<it>.pth of python -m lidar_rt_amd.train --refine-raydrop, or the "
+                    "reference's unet.pth): every frame's ray-drop probability is replaced by the network's output before the mask is formed (eval.py:129-144)")
+    ap.add_argument("--unet-backend", choices=("hip", "torch"), default=None, help="--unet: the HIP operator (liblrt_refine.so) or the module through torch; "
+                    "default: lidar_rt_amd.raydrop_refine.DEFAULT_CUDA_BACKEND (torch: the faster one at 64x2048, profiles/raydrop_refine.md)")
+    ap.add_argument("--unet-no-spatial", action="store_true", help="--unet: a network of 3 input channels (no ray origins and directions)")
     ap.add_argument("--sweep", choices=("off", "stored", "poses"), default="off", help="render with one pose per column (lidar_rt_amd.sweep), as python -m lidar_rt_amd.train "
                     "--sweep: stored = each frame's twist from its file, poses = twists derived from consecutive sensor poses")
     ap.add_argument("--sweep-ref", type=float, default=0.5, help="--sweep: the part of the sweep at which a frame's pose holds")

@@ -5,7 +5,8 @@
   the frames are ENQUEUED back to back (``Tracer.deferred_checks``), the overflow status of all of them is checked once at the end.
 * the metric set of eval.py:282-365 on device tensors: depth / intensity (rmse, mae, medae, ssim = skimage's 7x7 uniform-window
   structural_similarity with the ground truth's data range, psnr), ray-drop (rmse, accuracy, F1 at ``raydrop_ratio`` = 0.4), points (Chamfer distance and F-score at 5 cm through the package's own ``chamfer_3DDist``).
-  Not reproduced: LPIPS (needs pretrained network weights), the U-Net ray-drop refinement, image / point-cloud dumps.
+  Not reproduced: LPIPS (needs pretrained network weights), image / point-cloud dumps.  The U-Net ray-drop refinement (eval.py:129-144) is
+  ``refiner=``: a network packed by ``raydrop_refine.pack`` replaces each frame's ray-drop probability right after its render.
 * ``evaluate``       -- the loop of eval.py:370-470: per-frame metrics and their means.
 
 The Gaussian assets and the sensor are duck-typed like in ``renderer.raytracing`` (``training.GaussianScene`` / ``RangeFrames``).
@@ -21,9 +22,11 @@ from . import renderer
 
 
 def render_frames(gaussian_assets: Sequence, sensor, frame_ids: Iterable, background: torch.Tensor, args=None,
-                  check: bool = True) -> Dict[object, Dict[str, torch.Tensor]]:
+                  check: bool = True, refiner=None) -> Dict[object, Dict[str, torch.Tensor]]:
     """Forward-only renders of `frame_ids` (eval.py:124), no host synchronisation between frames.  Returns
-    ``{frame: {"depth", "intensity", "raydrop"}}`` (each (H, W, 1), detached)."""
+    ``{frame: {"depth", "intensity", "raydrop"}}`` (each (H, W, 1), detached).  `refiner`: a ray-drop refinement network
+    (``raydrop_refine.pack(net)``, or a bare ``RaydropUNet`` for the torch path): each frame's "raydrop" is replaced by
+    ``refine_raydrop`` of its render (eval.py:129-144), enqueued behind the render without a host wait."""
     if args is None:
         args = SimpleNamespace(dynamic=False, opt=SimpleNamespace(use_rayhit=False), pipe=SimpleNamespace())
     if renderer.tracer_2dgs is None:
@@ -38,6 +41,10 @@ def render_frames(gaussian_assets: Sequence, sensor, frame_ids: Iterable, backgr
             for f in frame_ids:
                 pkg = renderer.raytracing(f, gaussian_assets, sensor, background, args)
                 out[f] = {k: pkg[k].detach() for k in ("depth", "intensity", "raydrop")}
+                if refiner is not None:
+                    from . import raydrop_refine
+                    rays = sensor.get_range_rays(f) if refiner.in_channels == 9 else None
+                    out[f]["raydrop"] = raydrop_refine.refine_raydrop(out[f], rays, refiner)
         if check:
             tr.check()                                   # one wait for the whole batch; raises if any frame overflowed
     finally:
@@ -115,17 +122,18 @@ def fscore(dist1: torch.Tensor, dist2: torch.Tensor, threshold: float = 0.001):
 
 
 def evaluate(gaussian_assets: Sequence, sensor, frame_ids: Sequence, background: torch.Tensor, args=None,
-             raydrop_ratio: float = 0.4, use_gt_mask: bool = False, max_depth: float = 80.0, fused: bool = False) -> Dict[str, object]:
+             raydrop_ratio: float = 0.4, use_gt_mask: bool = False, max_depth: float = 80.0, refiner=None, fused: bool = False) -> Dict[str, object]:
     """Per-frame metrics and their means (eval.py:370-470; `raydrop_ratio` 0.4 as eval.py:72).  `sensor` offers get_depth /
     get_intensity / get_mask / inverse_projection_with_range like ``training.RangeFrames``.  As in ``record_render`` the rendered
     depth and the clamped rendered intensity are multiplied by the ray-hit mask (ground-truth or predicted, eval.py:184, :224, :238)
     before they are compared with the ground truth.  One device->host transfer at the end.  `fused`: every frame's figures from the
     HIP operator of ``lidar_rt_amd.metrics`` (one row of an (F, N) table per frame, no host wait between the frames) instead of the PyTorch
-    expressions below; the same dictionary."""
+    expressions below; the same dictionary.  `refiner`: see ``render_frames`` -- the refined probability forms the predicted mask and the
+    ray-drop figures, with `fused` or without."""
     if fused:
-        return _evaluate_fused(gaussian_assets, sensor, frame_ids, background, args, raydrop_ratio, use_gt_mask, max_depth)
+        return _evaluate_fused(gaussian_assets, sensor, frame_ids, background, args, raydrop_ratio, use_gt_mask, max_depth, refiner)
     frame_ids = list(frame_ids)
-    renders = render_frames(gaussian_assets, sensor, frame_ids, background, args)
+    renders = render_frames(gaussian_assets, sensor, frame_ids, background, args, refiner=refiner)
     per_frame: Dict[object, Dict[str, Dict[str, torch.Tensor]]] = {}
     for f in frame_ids:
         r = renders[f]
@@ -153,12 +161,12 @@ def evaluate(gaussian_assets: Sequence, sensor, frame_ids: Sequence, background:
     return {"frames": out_frames, "mean": mean}
 
 
-def _evaluate_fused(gaussian_assets, sensor, frame_ids, background, args, raydrop_ratio, use_gt_mask, max_depth) -> Dict[str, object]:
+def _evaluate_fused(gaussian_assets, sensor, frame_ids, background, args, raydrop_ratio, use_gt_mask, max_depth, refiner=None) -> Dict[str, object]:
     """`evaluate` with each frame's row from ``metrics.frame_metrics``; the table comes to the host in one transfer and the NaN-skipping means are
     formed there as in `evaluate`."""
     from . import metrics
     frame_ids = list(frame_ids)
-    renders = render_frames(gaussian_assets, sensor, frame_ids, background, args)
+    renders = render_frames(gaussian_assets, sensor, frame_ids, background, args, refiner=refiner)
     names = [gm for gm in metrics.ROW if gm not in metrics.EXTRAS]
     out_frames: Dict[object, Dict[str, Dict[str, float]]] = {}
     if frame_ids:

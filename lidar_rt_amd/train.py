@@ -31,6 +31,30 @@ def frame_of(seed: int, iteration: int, frames):
     return frames[random.Random(seed * 1_000_003 + iteration).randrange(len(frames))]
 
 
+def refine_stage(args, scene, seq, bg, dev, opt, iteration: int):
+    """train.py:386-447: the ray-drop refinement network trained on detached renders of the finished Gaussians (lidar_rt_amd.raydrop_refine);
+    writes unet<iteration>.pth, a plain state_dict in the reference's names, next to the checkpoint.  One process renders whole frames, with
+    the recorded sensor poses (also under --refine-poses): evaluate cannot load pose corrections, so these are the renders it will refine."""
+    from types import SimpleNamespace
+    from . import evaluation, raydrop_refine, renderer
+    rargs = SimpleNamespace(dynamic=bool(seq.meta.get("dynamic")), opt=SimpleNamespace(use_rayhit=bool(getattr(opt, "use_rayhit", False))), pipe=SimpleNamespace())
+    sharded, renderer.sharded = renderer.sharded, None
+    log = []
+    try:
+        def render_fn(frame):
+            return evaluation.render_frames(scene.gaussians_assets, seq.frames, [frame], bg, rargs)[frame]
+        net = raydrop_refine.train_refiner(render_fn, seq.frames, seq.train_frames, in_spatial=not args.refine_no_spatial, rot=bool(args.refine_rot),
+                                           epochs=args.refine_epochs, batch=args.refine_batch, seed=args.seed, channels=args.refine_channels, device=dev, log=log)
+    finally:
+        renderer.sharded = sharded
+    path = os.path.join(args.out, f"unet{iteration}.pth")
+    torch.save({k: v.detach().cpu() for k, v in net.state_dict().items()}, path)
+    print(json.dumps({"refine_raydrop": {"epochs": args.refine_epochs, "batch": args.refine_batch, "channels": args.refine_channels,
+                                         "in_channels": net.in_channels, "loss_first": log[0]["loss"] if log else None,
+                                         "loss_last": log[-1]["loss"] if log else None, "path": path}}), flush=True)
+    return net
+
+
 def run(args) -> dict:
     from . import renderer, sequence, training
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -45,7 +69,10 @@ def run(args) -> dict:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         backend = os.environ.get("LRT_DIST_BACKEND", "nccl")
-        dist.init_process_group(backend=backend, **({"device_id": dev} if backend == "nccl" else {}))
+        # --refine-raydrop: ranks > 0 wait at the final barrier while rank 0 trains the network, for longer than the default 10 minutes
+        import datetime
+        slow = {"timeout": datetime.timedelta(hours=24)} if getattr(args, "refine_raydrop", False) else {}
+        dist.init_process_group(backend=backend, **slow, **({"device_id": dev} if backend == "nccl" else {}))
         from .parallel import ShardedTracer
         renderer.sharded = ShardedTracer(exchange="sparse", deferred_accum=not args.exact_accum, deterministic=args.deterministic)
     renderer.deferred_accum = not args.exact_accum       # the loop reads the hit weights after loss.backward() only (train.py:156,219)
@@ -105,7 +132,10 @@ def run(args) -> dict:
     bg = torch.tensor([0.0, 0.0, 1.0], device=dev)       # the reference's background for (intensity, ray-hit, ray-drop): train.py:106
     log, t0 = [], time.perf_counter()
     res = {}
-    for it in range(first, args.iters + 1):
+    only_refine = bool(getattr(args, "only_refine", False))
+    if only_refine and not args.resume:
+        raise SystemExit("--only-refine needs --resume (the Gaussians it renders)")
+    for it in range(first, (first - 1 if only_refine else args.iters) + 1):
         torch.manual_seed(args.seed * 1_000_003 + it)      # the densification's random draws: a function of (seed, iteration) on every rank
         frame = frame_of(args.seed, it, seq.train_frames)
         res = training.training_step(scene, seq.frames, frame, it, opt, bg, dynamic=bool(seq.meta.get("dynamic")), poses=sensor_poses,
@@ -127,10 +157,14 @@ def run(args) -> dict:
     elif renderer.tracer_2dgs is not None:
         renderer.tracer_2dgs.check(dev)
     torch.cuda.synchronize()
+    unet = None
+    if getattr(args, "refine_raydrop", False) and rank == 0:
+        # after the last iteration; with --gpus N rank 0 alone runs it on whole frames while the others wait at the barrier below
+        unet = refine_stage(args, scene, seq, bg, dev, opt, first - 1 if only_refine else max(args.iters, first - 1))
     if world > 1:
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()
-    return {"log": log, "scene": scene, "sequence": seq, "last": res, "poses": sensor_poses, "boxes": box_poses}
+    return {"log": log, "scene": scene, "sequence": seq, "last": res, "poses": sensor_poses, "boxes": box_poses, "unet": unet}
 
 
 def main(argv=None) -> int:
@@ -193,7 +227,20 @@ def main(argv=None) -> int:
                     "read back by --resume; works with --gpus N")
     ap.add_argument("--box-lr-trans", type=float, default=1e-3, help="--refine-boxes: Adam learning rate of the translation part (m)")
     ap.add_argument("--box-lr-rot", type=float, default=1e-4, help="--refine-boxes: Adam learning rate of the rotation part (rad)")
+    ap.add_argument("--refine-raydrop", action="store_true", help="after the last iteration, train the ray-drop refinement U-Net on detached renders "
+                    "(lidar_rt_amd.raydrop_refine.train_refiner, the stage of the reference's train.py:386-447) and write unet<it>.pth, a plain state_dict in the "
+                    "reference's names, next to the checkpoint; python -m lidar_rt_amd.evaluate --unet reads it.  With --gpus N rank 0 alone runs it")
+    ap.add_argument("--refine-epochs", type=int, default=400, help="--refine-raydrop: Adam steps")
+    ap.add_argument("--refine-batch", type=int, default=16, help="--refine-raydrop: frames whose gradients are accumulated per Adam step")
+    ap.add_argument("--refine-rot", action="store_true", help="--refine-raydrop: roll every frame by a random number of columns, input and labels alike")
+    ap.add_argument("--refine-no-spatial", action="store_true", help="--refine-raydrop: 3 input channels (no ray origins and directions) instead of 9")
+    ap.add_argument("--refine-channels", type=int, default=32, help="--refine-raydrop: width of the network (the reference's is 32; a multiple of 8 for the HIP operator)")
+    ap.add_argument("--only-refine", action="store_true", help="with --resume and --refine-raydrop: skip the Gaussian loop and train the network on the checkpoint's renders")
     args = ap.parse_args(argv)
+    if args.only_refine and not (args.resume and args.refine_raydrop):
+        ap.error("--only-refine needs --resume and --refine-raydrop")
+    if args.refine_epochs < 1 or args.refine_batch < 1:
+        ap.error("--refine-epochs and --refine-batch must be positive")
     if args.refine_boxes and not os.path.exists(os.path.join(args.data, "boxes.npz")):
         ap.error(f"--refine-boxes: {args.data} has no tracking boxes (boxes.npz)")
     if not 3 <= args.init_knn <= 8:
