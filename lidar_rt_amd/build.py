@@ -115,6 +115,11 @@ REFINE_STAMP = os.path.join(CSRC, "liblrt_refine.srchash")
 REFINE_SOURCES = ["lrt_refine.hip"]
 REFINE_HEADERS = ["lrt_refine_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_refine.h")]
 
+SWEEPPROJ_LIB = os.path.join(CSRC, "liblrt_sweepproj.so")
+SWEEPPROJ_STAMP = os.path.join(CSRC, "liblrt_sweepproj.srchash")
+SWEEPPROJ_SOURCES = ["lrt_sweepproj.hip"]
+SWEEPPROJ_HEADERS = ["lrt_sweepproj_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_sweepproj.h")]
+
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
     """The library is rebuilt when it is missing or was compiled from OTHER sources: decided by the content hash written next to it,
@@ -502,6 +507,46 @@ def build_refine(force: bool = False, verbose: bool = False) -> str:
     return REFINE_LIB
 
 
+def sweepproj_source_hash() -> str:
+    """source_hash() of the sweep-projection library: over ITS sources, headers (the two rule headers it reads included) and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(SWEEPPROJ_SOURCES + SWEEPPROJ_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def sweepproj_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(SWEEPPROJ_LIB):
+        return True
+    try:
+        return open(SWEEPPROJ_STAMP).read().strip() != sweepproj_source_hash()
+    except OSError:
+        return True
+
+
+def build_sweepproj(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_sweepproj.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other ten libraries."""
+    if force or sweepproj_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", SWEEPPROJ_LIB] \
+            + [os.path.join(CSRC, s) for s in SWEEPPROJ_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(SWEEPPROJ_STAMP, "w") as f:
+            f.write(sweepproj_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(SWEEPPROJ_LIB)} is up to date (sources {sweepproj_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(SWEEPPROJ_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return SWEEPPROJ_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -606,6 +651,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_project(force, verbose)
     build_sweep(force, verbose)
     build_refine(force, verbose)
+    build_sweepproj(force, verbose)
     return lib
 
 
