@@ -36,6 +36,12 @@
 * ``csrc/liblrt_refine.so`` -- the inference of the ray-drop refinement network (``csrc/lrt_refine.hip``, C ABI ``include/lrt_refine.h``): a tenth
   product library on the same pattern.  Loaded by ``lidar_rt_amd.raydrop_refine``.
 
+* ``csrc/liblrt_sweepproj.so`` -- the range-image projection under the sweep model (``csrc/lrt_sweepproj.hip``, C ABI ``include/lrt_sweepproj.h``): an
+  eleventh product library on the same pattern.  Loaded by ``lidar_rt_amd.sweep_project``.
+
+* ``csrc/liblrt_unproject.so`` -- the point clouds of range images (``csrc/lrt_unproject.hip``, C ABI ``include/lrt_unproject.h``): a twelfth product
+  library on the same pattern.  Loaded by ``lidar_rt_amd.unproject``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -119,6 +125,11 @@ SWEEPPROJ_LIB = os.path.join(CSRC, "liblrt_sweepproj.so")
 SWEEPPROJ_STAMP = os.path.join(CSRC, "liblrt_sweepproj.srchash")
 SWEEPPROJ_SOURCES = ["lrt_sweepproj.hip"]
 SWEEPPROJ_HEADERS = ["lrt_sweepproj_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_sweepproj.h")]
+# the un-projection library: once more
+UNPROJECT_LIB = os.path.join(CSRC, "liblrt_unproject.so")
+UNPROJECT_STAMP = os.path.join(CSRC, "liblrt_unproject.srchash")
+UNPROJECT_SOURCES = ["lrt_unproject.hip"]
+UNPROJECT_HEADERS = ["lrt_unproject_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_unproject.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -547,6 +558,46 @@ def build_sweepproj(force: bool = False, verbose: bool = False) -> str:
     return SWEEPPROJ_LIB
 
 
+def unproject_source_hash() -> str:
+    """source_hash() of the un-projection library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(UNPROJECT_SOURCES + UNPROJECT_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def unproject_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(UNPROJECT_LIB):
+        return True
+    try:
+        return open(UNPROJECT_STAMP).read().strip() != unproject_source_hash()
+    except OSError:
+        return True
+
+
+def build_unproject(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_unproject.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other eleven libraries."""
+    if force or unproject_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", UNPROJECT_LIB] \
+            + [os.path.join(CSRC, s) for s in UNPROJECT_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(UNPROJECT_STAMP, "w") as f:
+            f.write(unproject_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(UNPROJECT_LIB)} is up to date (sources {unproject_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(UNPROJECT_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return UNPROJECT_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -652,6 +703,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_sweep(force, verbose)
     build_refine(force, verbose)
     build_sweepproj(force, verbose)
+    build_unproject(force, verbose)
     return lib
 
 

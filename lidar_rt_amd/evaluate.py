@@ -7,7 +7,7 @@ computes the metric set of eval.py:282-365 (depth / intensity: rmse, mae, medae,
 and F-score through the package's own Chamfer operator) and prints ONE JSON object ``{"iteration", "frames", "mean", "per_frame"}``; ``--out`` also
 writes it to a file.  ``--unet PATH`` puts the ray-drop refinement network (``lidar_rt_amd.raydrop_refine``; a ``unet<it>.pth`` of ``python -m
 lidar_rt_amd.train --refine-raydrop`` or the reference's ``unet.pth``) behind every render, as eval.py:129-144 does -- with the stored batch-norm
-statistics and without dropout.  Not reproduced (``evaluation.py``): LPIPS, image / point-cloud dumps.
+statistics and without dropout.  Not reproduced (``evaluation.py``): LPIPS, image dumps; the renders' point clouds are written by ``python -m lidar_rt_amd.simulate``.
 """
 from __future__ import annotations
 

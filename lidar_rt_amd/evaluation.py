@@ -5,7 +5,7 @@
   the frames are ENQUEUED back to back (``Tracer.deferred_checks``), the overflow status of all of them is checked once at the end.
 * the metric set of eval.py:282-365 on device tensors: depth / intensity (rmse, mae, medae, ssim = skimage's 7x7 uniform-window
   structural_similarity with the ground truth's data range, psnr), ray-drop (rmse, accuracy, F1 at ``raydrop_ratio`` = 0.4), points (Chamfer distance and F-score at 5 cm through the package's own ``chamfer_3DDist``).
-  Not reproduced: LPIPS (needs pretrained network weights), image / point-cloud dumps.  The U-Net ray-drop refinement (eval.py:129-144) is
+  Not reproduced: LPIPS (needs pretrained network weights), image dumps; the point clouds of the renders are ``python -m lidar_rt_amd.simulate``.  The U-Net ray-drop refinement (eval.py:129-144) is
   ``refiner=``: a network packed by ``raydrop_refine.pack`` replaces each frame's ray-drop probability right after its render.
 * ``evaluate``       -- the loop of eval.py:370-470: per-frame metrics and their means.
 
@@ -22,11 +22,12 @@ from . import renderer
 
 
 def render_frames(gaussian_assets: Sequence, sensor, frame_ids: Iterable, background: torch.Tensor, args=None,
-                  check: bool = True, refiner=None) -> Dict[object, Dict[str, torch.Tensor]]:
+                  check: bool = True, refiner=None, decomp=False) -> Dict[object, Dict[str, torch.Tensor]]:
     """Forward-only renders of `frame_ids` (eval.py:124), no host synchronisation between frames.  Returns
     ``{frame: {"depth", "intensity", "raydrop"}}`` (each (H, W, 1), detached).  `refiner`: a ray-drop refinement network
     (``raydrop_refine.pack(net)``, or a bare ``RaydropUNet`` for the torch path): each frame's "raydrop" is replaced by
-    ``refine_raydrop`` of its render (eval.py:129-144), enqueued behind the render without a host wait."""
+    ``refine_raydrop`` of its render (eval.py:129-144), enqueued behind the render without a host wait.  `decomp`: ``renderer.raytracing``'s
+    ("background" / "object": that part of the scene alone)."""
     if args is None:
         args = SimpleNamespace(dynamic=False, opt=SimpleNamespace(use_rayhit=False), pipe=SimpleNamespace())
     if renderer.tracer_2dgs is None:
@@ -39,7 +40,7 @@ def render_frames(gaussian_assets: Sequence, sensor, frame_ids: Iterable, backgr
     try:
         with torch.no_grad():
             for f in frame_ids:
-                pkg = renderer.raytracing(f, gaussian_assets, sensor, background, args)
+                pkg = renderer.raytracing(f, gaussian_assets, sensor, background, args, decomp=decomp)
                 out[f] = {k: pkg[k].detach() for k in ("depth", "intensity", "raydrop")}
                 if refiner is not None:
                     from . import raydrop_refine
