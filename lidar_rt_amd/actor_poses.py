@@ -165,6 +165,7 @@ class CorrectedBox:
     def __init__(self, poses: ActorPoses, a: int):
         self.poses, self.a, self.box = poses, a, poses.boxes[a]
         self.min_xyz, self.max_xyz = self.box.min_xyz, self.box.max_xyz
+        self.twist = getattr(self.box, "twist", {})                # the actor's motion within a sweep (lidar_rt_amd.actor_sweep): the box's own dict
         self.frame = _CorrectedFrames(self)
 
 

@@ -42,6 +42,9 @@
 * ``csrc/liblrt_unproject.so`` -- the point clouds of range images (``csrc/lrt_unproject.hip``, C ABI ``include/lrt_unproject.h``): a twelfth product
   library on the same pattern.  Loaded by ``lidar_rt_amd.unproject``.
 
+* ``csrc/liblrt_actorsweep.so`` -- actors that move within a sweep (``csrc/lrt_actorsweep.hip``, C ABI ``include/lrt_actorsweep.h``): a thirteenth
+  product library on the same pattern.  Loaded by ``lidar_rt_amd.actor_sweep``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -130,6 +133,12 @@ UNPROJECT_LIB = os.path.join(CSRC, "liblrt_unproject.so")
 UNPROJECT_STAMP = os.path.join(CSRC, "liblrt_unproject.srchash")
 UNPROJECT_SOURCES = ["lrt_unproject.hip"]
 UNPROJECT_HEADERS = ["lrt_unproject_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_unproject.h")]
+# the actor-sweep library: once more (it reads the rule headers of the projection and the two sweep libraries; their hashes do not read back)
+ACTORSWEEP_LIB = os.path.join(CSRC, "liblrt_actorsweep.so")
+ACTORSWEEP_STAMP = os.path.join(CSRC, "liblrt_actorsweep.srchash")
+ACTORSWEEP_SOURCES = ["lrt_actorsweep.hip"]
+ACTORSWEEP_HEADERS = ["lrt_actorsweep_math.h", "lrt_sweepproj_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h",
+                      os.path.join("..", "..", "include", "lrt_actorsweep.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -598,6 +607,46 @@ def build_unproject(force: bool = False, verbose: bool = False) -> str:
     return UNPROJECT_LIB
 
 
+def actorsweep_source_hash() -> str:
+    """source_hash() of the actor-sweep library: over ITS sources, headers (the rule headers it reads included) and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(ACTORSWEEP_SOURCES + ACTORSWEEP_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def actorsweep_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(ACTORSWEEP_LIB):
+        return True
+    try:
+        return open(ACTORSWEEP_STAMP).read().strip() != actorsweep_source_hash()
+    except OSError:
+        return True
+
+
+def build_actorsweep(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_actorsweep.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other twelve libraries."""
+    if force or actorsweep_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", ACTORSWEEP_LIB] \
+            + [os.path.join(CSRC, s) for s in ACTORSWEEP_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(ACTORSWEEP_STAMP, "w") as f:
+            f.write(actorsweep_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(ACTORSWEEP_LIB)} is up to date (sources {actorsweep_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(ACTORSWEEP_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return ACTORSWEEP_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -704,6 +753,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_refine(force, verbose)
     build_sweepproj(force, verbose)
     build_unproject(force, verbose)
+    build_actorsweep(force, verbose)
     return lib
 
 

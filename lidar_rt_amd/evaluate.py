@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 import sys
 from types import SimpleNamespace
 
@@ -26,7 +27,18 @@ def run(args) -> dict:
     dev = torch.device("cuda", args.device)
     torch.cuda.set_device(dev)
     seq = sequence.load_sequence(args.data, dev, sweep=getattr(args, "sweep", "off"), sweep_fraction=getattr(args, "sweep_fraction", 1.0),
-                                 sweep_ref=getattr(args, "sweep_ref", 0.5), sweep_direction=getattr(args, "sweep_direction", "cw"))
+                                 sweep_ref=getattr(args, "sweep_ref", 0.5), sweep_direction=getattr(args, "sweep_direction", "cw"),
+                                 actor_sweep=getattr(args, "actor_sweep", "off"))
+    if getattr(args, "actor_sweep", "off") != "off":
+        # the actors move within a sweep too (lidar_rt_amd.actor_sweep); --actor-twists: the twists python -m lidar_rt_amd.train --refine-actor-twist learnt
+        from . import renderer
+        renderer.actor_sweep = True
+        sibling = os.path.join(os.path.dirname(os.path.abspath(args.ckpt)), os.path.basename(args.ckpt).replace("chkpnt", "actor_twists"))
+        if not getattr(args, "actor_twists", None) and sibling != os.path.abspath(args.ckpt) and os.path.exists(sibling):
+            print(f"[evaluate] note: learnt actor twists lie beside {args.ckpt}; they are used only when given with --actor-twists", file=sys.stderr, flush=True)
+        if getattr(args, "actor_twists", None):
+            for (a, f), v in torch.load(args.actor_twists, map_location=dev, weights_only=False)["eta"].items():
+                seq.boxes[a].twist[f] = v.to(dev)
     opt = training.default_options()
     scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed)
     scene.training_setup(opt)
@@ -95,8 +107,15 @@ def main(argv=None) -> int:
     ap.add_argument("--sweep-ref", type=float, default=0.5, help="--sweep: the part of the sweep at which a frame's pose holds")
     ap.add_argument("--sweep-direction", choices=("cw", "ccw"), default="cw", help="--sweep: cw = time rises with the column index")
     ap.add_argument("--sweep-fraction", type=float, default=1.0, help="--sweep poses: the part of the time between two consecutive frame ids that one sweep takes")
+    ap.add_argument("--actor-sweep", choices=("off", "stored", "boxes"), default="off", help="the actors move within a sweep too (lidar_rt_amd.actor_sweep), as "
+                    "python -m lidar_rt_amd.train --actor-sweep; needs a --sweep")
+    ap.add_argument("--actor-twists", default=None, help="--actor-sweep: learnt twists (actor_twists<it>.pth of python -m lidar_rt_amd.train --refine-actor-twist)")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     args = ap.parse_args(argv)
+    if args.actor_sweep != "off" and args.sweep == "off":
+        ap.error("--actor-sweep needs a sweep (--sweep stored or --sweep poses)")
+    if args.actor_twists and args.actor_sweep == "off":
+        ap.error("--actor-twists needs --actor-sweep")
     res = run(args)
     txt = json.dumps(res)
     print(txt, flush=True)

@@ -39,6 +39,13 @@ deterministic = False
 
 use_fused_preprocess = True   # module switch: False forces the getter chain of the reference (used by the tests)
 
+# Actors that move within a sweep (addition; default off): True runs lidar_rt_amd.actor_sweep.actor_sweep on the concatenated `_xyz` / `_rotation` in
+# front of the fused pre-processing, for a frame with sweep rays (`sweep_meta` and `pose_meta` of the RangeFrames; a SensorPoses gives its current
+# pose and twist, detached) whose posed assets carry a twist for it (`bounding_box.twist[frame]`, sequence.TrackingBox).  A no-op otherwise; with
+# all twists zero the stage passes every Gaussian through bit for bit.  The same on every rank: azimuth sharding needs nothing new.
+actor_sweep = False
+last_actor_sweep = None       # the `info` (column, counts: device tensors) of the last stage that ran, for logging
+
 # Multi-GPU: set to a lidar_rt_amd.parallel.ShardedTracer and raytracing() traces this rank's azimuth slab only, all-gathers the
 # image and, in the backward, exchanges the gradient rows so that EVERY rank holds the full image, the full gradients and the full
 # `accum_gaussian_weight` -- train.py's loop (losses, scene.optimize: Adam, densification, pruning) then runs unchanged and identically
@@ -74,7 +81,46 @@ class _ShardedTrace(torch.autograd.Function):
                 g["opacities"].reshape(opacity.shape).clone(), g["shs"].clone(), None, None, None, None, None)
 
 
-def _fused_inputs(frame, assets, dynamic, decomp):
+def _sensor_motion(frame, sensor):
+    """(sensor2world, twist, tau, W, data_type, sensor2ego on the host) of a frame with sweep rays, else None."""
+    if isinstance(sensor, tuple) or sensor is None:
+        return None
+    frames = getattr(sensor, "frames", sensor)             # a poses.SensorPoses wraps the RangeFrames
+    pose_meta, sweep_meta = getattr(frames, "pose_meta", {}), getattr(frames, "sweep_meta", {})
+    if frame not in pose_meta or frame not in sweep_meta:
+        return None
+    _, s2w, data_type, s2e = pose_meta[frame]
+    twist, tau = sweep_meta[frame]
+    if frames is not sensor and frame in getattr(sensor, "xi", {}):      # the current values of a refined sensor
+        s2w = sensor.sensor2world(frame)
+        twist = sensor.twist.get(frame, twist)
+    cache = frames.__dict__.setdefault("_actor_sweep_conventions", {})      # on the frames themselves: read back once per frame, gone with them
+    conv = cache.get(frame)
+    if conv is None:
+        host = None if (data_type != "Waymo" or s2e is None) else torch.as_tensor(s2e).detach().to("cpu", torch.float32)
+        conv = cache[frame] = (data_type, host)
+    return s2w.detach(), twist.detach(), tau, int(tau.numel()), conv[0], conv[1]
+
+
+def _actor_sweep_stage(frame, assets, poses, sensor, seg, tab, xyz, rot):
+    """xyz and rot advanced to every Gaussian's instant (lidar_rt_amd.actor_sweep), or themselves when the frame has no sweep or no posed asset a twist."""
+    global last_actor_sweep
+    motion = _sensor_motion(frame, sensor)
+    if motion is None:
+        return xyz, rot
+    rows = [None if ps is None else getattr(getattr(pc, "bounding_box", None), "twist", {}).get(frame) for pc, ps in zip(assets, poses)]
+    if all(t is None for t in rows):
+        return xyz, rot
+    from .actor_sweep import actor_sweep as stage
+    dev = xyz.device
+    zero = torch.zeros(6, dtype=torch.float32, device=dev)
+    twists = torch.stack([zero if t is None else t.to(device=dev, dtype=torch.float32).reshape(6) for t in rows])
+    s2w, xi, tau, W, data_type, s2e = motion
+    xyz_s, rot_s, last_actor_sweep = stage(xyz, rot, seg, tab.detach(), twists, s2w, xi, tau, W, data_type, s2e)
+    return xyz_s, rot_s
+
+
+def _fused_inputs(frame, assets, dynamic, decomp, sensor=None):
     """Raw parameters of GaussianModel-like assets (`_xyz`, `_scaling`, `_rotation`, `_opacity`, `bounding_box.frame`)
     through lidar_rt_amd.preprocess.fused_activations; None when an asset does not expose them or when the reference
     would treat its position and its rotation inconsistently (posed means without a composed rotation or vice versa)."""
@@ -95,7 +141,10 @@ def _fused_inputs(frame, assets, dynamic, decomp):
     dev = assets[0]._xyz.device
     seg, tab = pack_poses(poses, counts, dev)
     cat = (lambda name: torch.cat([getattr(pc, name) for pc in assets], 0)) if len(assets) > 1 else (lambda name: getattr(assets[0], name))
-    return fused_activations(cat("_xyz"), cat("_scaling"), cat("_rotation"), cat("_opacity"), seg, tab)
+    xyz, rot = cat("_xyz"), cat("_rotation")
+    if actor_sweep:
+        xyz, rot = _actor_sweep_stage(frame, assets, poses, sensor, seg, tab, xyz, rot)
+    return fused_activations(xyz, cat("_scaling"), rot, cat("_opacity"), seg, tab)
 
 
 def raytracing(frame, gaussian_assets, sensor, background, args, scaling_modifier=1.0, override_color=None,
@@ -127,7 +176,7 @@ def raytracing(frame, gaussian_assets, sensor, background, args, scaling_modifie
     settings = TracingSettings(None, None, None, None, background.to(dev, torch.float32), 1.0, e, e,
                                gaussian_assets[0].active_sh_degree, sensor_center.to(dev), False, False)
     dynamic = bool(getattr(args, "dynamic", False))
-    fused = _fused_inputs(frame, gaussian_assets, dynamic, decomp) if use_fused_preprocess else None
+    fused = _fused_inputs(frame, gaussian_assets, dynamic, decomp, sensor) if use_fused_preprocess else None
     if fused is not None:
         # one HIP launch for activations + actor transforms + quaternion composition + concatenation (and one for its backward)
         means3D, scales, rotations, opacity = fused

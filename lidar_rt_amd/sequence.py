@@ -12,6 +12,7 @@ in-memory ``RangeFrames`` / ``GaussianScene`` of ``lidar_rt_amd.training``:
                                   | inclination (2,) bounds or (H,) per-beam table [rad] | sensor2world (4,4) f32
     DIR/boxes.npz      (optional) frames (F,) i64 | translation (A,F,3) f32 | quaternion (A,F,4) f32 (w,x,y,z: actor -> world)
                                   | valid (A,F) bool | size (A,3) f32 [tracking-box extents, metres]
+                                  | twist (A,F,6) f32 (optional): every actor's motion over one sweep in its own frame (lidar_rt_amd.actor_sweep)
     DIR/init/background.npz, DIR/init/actor_00.npz ...   (optional) points (N,3) f32 [world / actor frame] | intensity (N,) f32
                                   | normals (N,3) f32 (optional): the initial point clouds (gaussian_model.py:155-184); without them the
                                   background is initialised from the back-projected returns of the training frames, an actor from
@@ -46,6 +47,7 @@ class TrackingBox:
         half = 0.5 * torch.as_tensor(np.asarray(size, np.float32), device=device)
         self.min_xyz, self.max_xyz = -half, half
         self.frame: Dict[int, tuple] = {}
+        self.twist: Dict[int, torch.Tensor] = {}     # optional: frame -> (6,) the actor's motion over one sweep in its own frame (lidar_rt_amd.actor_sweep)
 
 
 def _frame_path(root: str, fid: int) -> str:
@@ -87,7 +89,8 @@ def write_sequence(root: str, frames: Iterable[dict], data_type: str = "KITTI", 
         F_ = len(boxes["frames"])
         np.savez(os.path.join(root, "boxes.npz"), frames=np.asarray(boxes["frames"], np.int64), translation=npy(boxes["translation"]).reshape(A, F_, 3),
                  quaternion=npy(boxes["quaternion"]).reshape(A, F_, 4), valid=npy(boxes.get("valid", np.ones((A, F_), bool)), np.bool_).reshape(A, F_),
-                 size=npy(boxes["size"]).reshape(A, 3))
+                 size=npy(boxes["size"]).reshape(A, 3),
+                 **({} if boxes.get("twist") is None else {"twist": npy(boxes["twist"]).reshape(A, F_, 6)}))      # moving actors: written only when given
     if init:
         os.makedirs(os.path.join(root, "init"), exist_ok=True)
         for name, cloud in init.items():
@@ -105,6 +108,7 @@ def write_sequence(root: str, frames: Iterable[dict], data_type: str = "KITTI", 
 
 
 SWEEP_MODES = (None, "off", "stored", "poses")
+ACTOR_SWEEP_MODES = (None, "off", "stored", "boxes")
 
 
 def pose_twists(root: str, ids: Sequence[int], sweep_fraction: float = 1.0) -> Dict[int, np.ndarray]:
@@ -125,13 +129,19 @@ def pose_twists(root: str, ids: Sequence[int], sweep_fraction: float = 1.0) -> D
 
 
 def load_sequence(root: str, device="cuda", frames: Optional[Sequence[int]] = None, sweep: Optional[str] = None, sweep_fraction: float = 1.0,
-                  sweep_ref: float = 0.5, sweep_direction: str = "cw") -> SimpleNamespace:
+                  sweep_ref: float = 0.5, sweep_direction: str = "cw", actor_sweep: Optional[str] = None) -> SimpleNamespace:
     """-> namespace(meta, frames: RangeFrames, boxes: [TrackingBox], init: {name: {points, intensity, normals}}, train_frames, test_frames).
     The ray grids are derived from inclination + pose like ``LiDARSensor.get_range_rays`` does (RangeFrames.range_rays).
 
     ``sweep``: None (or "off") -- one pose per frame, as ever; "stored" -- every frame's ``twist`` (and ``tau``, else
     ``sweep.column_times(W, sweep_ref, sweep_direction)``) from its file, a frame without one is refused; "poses" -- the twists of
-    ``pose_twists(root, meta["frames"], sweep_fraction)``.  With a sweep the rays are ``sweep.sweep_rays``: one pose per column."""
+    ``pose_twists(root, meta["frames"], sweep_fraction)``.  With a sweep the rays are ``sweep.sweep_rays``: one pose per column.
+
+    ``actor_sweep``: None (or "off") -- the boxes carry no twists, as ever; "stored" -- ``TrackingBox.twist`` from the box file's ``twist``, a file
+    without one is refused; "boxes" -- ``actor_sweep.actor_twists_from_boxes`` over ALL frames of the box file with ``sweep_fraction``."""
+    if actor_sweep not in ACTOR_SWEEP_MODES:
+        raise ValueError(f"load_sequence: actor_sweep {actor_sweep!r} (None, 'off', 'stored' or 'boxes')")
+    actor_sweep = None if actor_sweep == "off" else actor_sweep
     if sweep not in SWEEP_MODES:
         raise ValueError(f"load_sequence: sweep {sweep!r} (None, 'off', 'stored' or 'poses')")
     sweep = None if sweep == "off" else sweep
@@ -177,7 +187,17 @@ def load_sequence(root: str, device="cuda", frames: Optional[Sequence[int]] = No
             for k, fid in enumerate(fids):
                 if z["valid"][a, k]:
                     tb.frame[fid] = (torch.as_tensor(z["translation"][a, k], device=dev), torch.as_tensor(z["quaternion"][a, k], device=dev).reshape(1, 4), None, None)
+                    if actor_sweep == "stored":
+                        if "twist" not in z.files:
+                            raise ValueError(f"{bp}: no stored actor twists (actor_sweep='stored' needs them; actor_sweep='boxes' derives them from the boxes)")
+                        tb.twist[fid] = torch.as_tensor(z["twist"][a, k].astype(np.float32), device=dev)
             boxes.append(tb)
+        if actor_sweep == "boxes":
+            from .actor_sweep import actor_twists_from_boxes
+            for tb, tw in zip(boxes, actor_twists_from_boxes(boxes, fids, sweep_fraction)):
+                tb.twist = {f: torch.as_tensor(v.astype(np.float32), device=dev) for f, v in tw.items()}
+    elif actor_sweep is not None:
+        raise ValueError(f"{root}: actor_sweep={actor_sweep!r} needs tracking boxes (there is no boxes.npz)")
     init = {}
     ip = os.path.join(root, "init")
     if os.path.isdir(ip):
@@ -187,7 +207,7 @@ def load_sequence(root: str, device="cuda", frames: Optional[Sequence[int]] = No
                 init[fn[:-4]] = {k: torch.as_tensor(z[k], device=dev) for k in z.files}
     test = [t for t in meta.get("test_frames", []) if t in rf.rays]
     train = [f for f in sorted(rf.rays) if f not in set(test)] or sorted(rf.rays)
-    return SimpleNamespace(meta=meta, frames=rf, boxes=boxes, init=init, train_frames=train, test_frames=test, root=root, sweep=sweep)
+    return SimpleNamespace(meta=meta, frames=rf, boxes=boxes, init=init, train_frames=train, test_frames=test, root=root, sweep=sweep, actor_sweep=actor_sweep)
 
 
 def scene_from_sequence(seq: SimpleNamespace, max_sh_degree: int = 3, max_points: int = 2_000_000, seed: int = 0, init_from_frames: bool = False,

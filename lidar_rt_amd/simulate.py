@@ -70,6 +70,7 @@ class _MovedBox:
     def __init__(self, box, frame: dict):
         self.min_xyz, self.max_xyz = box.min_xyz, box.max_xyz
         self.frame = frame
+        self.twist = getattr(box, "twist", {})       # the body twists are the box's own: a move multiplies on the world side, A' Exp(s eta) = M A Exp(s eta)
 
 
 def _quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -360,7 +361,7 @@ def simulate(data: str, ckpt: str, out: str, frames: str = "test", max_frames: i
              poses: Optional[str] = None, remove_actor: Sequence[int] = (), move_actor: Sequence[Sequence[float]] = (), only: Optional[str] = None,
              frame: str = "world", fmt: str = "bin", fields: str = "xyzi", sequence_dir: Optional[str] = None, backend: Optional[str] = None,
              min_depth: float = 0.0, max_depth: Optional[float] = None, max_points: int = 2_000_000, seed: int = 0, device: int = 0,
-             origin_shift: bool = True) -> dict:
+             origin_shift: bool = True, actor_sweep: str = "off", actor_twists: Optional[str] = None) -> dict:
     """The run behind the command (see the module text); returns what ``OUT/simulate.json`` holds.  ``origin_shift=False``: the tables of a moving
     sensor are the plain inverses of pose, twist and ``tau`` (``column_transforms`` without ``origins``)."""
     from . import evaluate as evaluate_mod
@@ -375,6 +376,12 @@ def simulate(data: str, ckpt: str, out: str, frames: str = "test", max_frames: i
         raise SimulateError("simulate: --inclination and --inclination-table exclude each other")
     if (height is not None and height < 1) or (width is not None and width < 1):
         raise SimulateError(f"simulate: a sensor of {height} x {width} pixels")
+    if actor_sweep not in ("off", "stored", "boxes"):
+        raise SimulateError(f"simulate: actor_sweep {actor_sweep!r} (off, stored or boxes)")
+    if actor_sweep != "off" and sweep in (None, "off"):
+        raise SimulateError("simulate: --actor-sweep needs a moving sensor (--sweep): the instants are those of its columns")
+    if actor_twists and actor_sweep == "off":
+        raise SimulateError("simulate: --actor-twists needs --actor-sweep")
     if fmt not in ("bin", "npy") or fields not in ("xyzi", "xyzirt"):
         raise SimulateError(f"simulate: format {fmt!r} (bin or npy), fields {fields!r} (xyzi or xyzirt)")
     with open(os.path.join(data, "meta.json")) as fh:                       # the arguments are judged before the device is touched
@@ -387,7 +394,11 @@ def simulate(data: str, ckpt: str, out: str, frames: str = "test", max_frames: i
         raise SystemExit("lidar_rt_amd.simulate needs a HIP device (there is no CPU path for the render)")
     dev = torch.device("cuda", device)
     torch.cuda.set_device(dev)
-    seq = sequence_mod.load_sequence(data, dev, sweep=sweep, sweep_fraction=sweep_fraction, sweep_ref=sweep_ref, sweep_direction=sweep_direction)
+    seq = sequence_mod.load_sequence(data, dev, sweep=sweep, sweep_fraction=sweep_fraction, sweep_ref=sweep_ref, sweep_direction=sweep_direction,
+                                     actor_sweep=actor_sweep)
+    if actor_twists:                                                        # what python -m lidar_rt_amd.train --refine-actor-twist learnt
+        for (a_, f_), v in torch.load(actor_twists, map_location=dev, weights_only=False)["eta"].items():
+            seq.boxes[a_].twist[f_] = v.to(dev)
     opt = training.default_options()
     scene = sequence_mod.scene_from_sequence(seq, max_points=max_points, seed=seed)
     scene.training_setup(opt)
@@ -408,7 +419,13 @@ def simulate(data: str, ckpt: str, out: str, frames: str = "test", max_frames: i
     sensor = build_sensor(seq, ids, height, width, inclination, mount, new_poses, sweep_ref, sweep_direction, sweep_fraction)
     bg = torch.tensor([0.0, 0.0, 1.0], device=dev)
     rargs = SimpleNamespace(dynamic=bool(seq.meta.get("dynamic")), opt=SimpleNamespace(use_rayhit=bool(getattr(opt, "use_rayhit", False))), pipe=SimpleNamespace())
-    renders = evaluation.render_frames(assets, sensor, ids, bg, rargs, refiner=refiner, decomp=decomp)
+    from . import renderer
+    before = renderer.actor_sweep
+    renderer.actor_sweep = actor_sweep != "off"                             # every Gaussian of a moving actor at its own instant (lidar_rt_amd.actor_sweep)
+    try:
+        renders = evaluation.render_frames(assets, sensor, ids, bg, rargs, refiner=refiner, decomp=decomp)
+    finally:
+        renderer.actor_sweep = before
     H, W = (int(x) for x in sensor.get_range_rays(ids[0])[0].shape[:2])
     pose_of = {f: sensor.pose_meta[f][1].detach().cpu().numpy().astype(np.float64) for f in ids}
     sw = {f: tuple(t.detach().cpu().numpy() for t in sensor.sweep_meta[f]) for f in ids if f in sensor.sweep_meta}
@@ -423,7 +440,8 @@ def simulate(data: str, ckpt: str, out: str, frames: str = "test", max_frames: i
               "arguments": {"data": data, "ckpt": ckpt, "frames": frames, "max_frames": max_frames, "raydrop_ratio": raydrop_ratio, "boxes": boxes, "unet": unet,
                             "sweep": sweep, "sweep_ref": sweep_ref, "sweep_direction": sweep_direction, "sweep_fraction": sweep_fraction, "height": height,
                             "width": width, "inclination": inclination, "mount": None if mount is None else [float(x) for x in mount], "poses": poses,
-                            "min_depth": min_depth, "max_depth": max_depth, "backend": backend, "origin_shift": bool(origin_shift)},
+                            "min_depth": min_depth, "max_depth": max_depth, "backend": backend, "origin_shift": bool(origin_shift),
+                            "actor_sweep": actor_sweep, "actor_twists": actor_twists},
               **({"twists": {str(f): [float(x) for x in sw[f][0]] for f in sw}, "tau": {str(f): [float(x) for x in sw[f][1]] for f in sw}} if sw else {})}
     with open(os.path.join(out, "simulate.json"), "w") as fh:
         json.dump(report, fh, indent=1)
@@ -464,6 +482,9 @@ def main(argv=None) -> int:
     ap.add_argument("--sweep-ref", type=float, default=0.5)
     ap.add_argument("--sweep-direction", choices=("cw", "ccw"), default="cw")
     ap.add_argument("--sweep-fraction", type=float, default=1.0)
+    ap.add_argument("--actor-sweep", choices=("off", "stored", "boxes"), default="off", help="the actors move within a sweep too (lidar_rt_amd.actor_sweep), as "
+                    "python -m lidar_rt_amd.evaluate --actor-sweep; needs a --sweep.  --move-actor keeps an actor's twist: it is a motion in the actor's own frame")
+    ap.add_argument("--actor-twists", default=None, help="--actor-sweep: learnt twists (actor_twists<it>.pth of python -m lidar_rt_amd.train --refine-actor-twist)")
     ap.add_argument("--height", type=int, default=None, help="rows of the simulated sensor (default: the sequence's)")
     ap.add_argument("--width", type=int, default=None, help="columns of the simulated sensor (default: the sequence's)")
     g = ap.add_mutually_exclusive_group()

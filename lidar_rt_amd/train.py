@@ -80,7 +80,10 @@ def run(args) -> dict:
 
     # --sweep: one pose per column (lidar_rt_amd.sweep); callers that build `args` themselves need not know the switches
     seq = sequence.load_sequence(args.data, dev, sweep=getattr(args, "sweep", "off"), sweep_fraction=getattr(args, "sweep_fraction", 1.0),
-                                 sweep_ref=getattr(args, "sweep_ref", 0.5), sweep_direction=getattr(args, "sweep_direction", "cw"))
+                                 sweep_ref=getattr(args, "sweep_ref", 0.5), sweep_direction=getattr(args, "sweep_direction", "cw"),
+                                 actor_sweep=getattr(args, "actor_sweep", "off"))
+    # --actor-sweep: every Gaussian of a moving actor at the instant the sweep passes over it (lidar_rt_amd.actor_sweep), in front of the fused pre-processing
+    renderer.actor_sweep = getattr(args, "actor_sweep", "off") != "off"
     opt = training.default_options()
     for kv in args.opt:
         k, v = kv.split("=", 1)
@@ -118,6 +121,11 @@ def run(args) -> dict:
         from .actor_poses import ActorPoses
         box_poses = ActorPoses(seq.boxes, seq.train_frames, lr_trans=args.box_lr_trans, lr_rot=args.box_lr_rot)
         box_poses.install(scene.gaussians_assets)
+    actor_twists = None
+    if getattr(args, "refine_actor_twist", False):
+        # one twist per (actor, training frame), learnt through the gradient of the actor-sweep stage; saved beside each checkpoint
+        from .actor_sweep import ActorTwists
+        actor_twists = ActorTwists(seq.boxes, seq.train_frames, lr_trans=args.actor_twist_lr_trans, lr_rot=args.actor_twist_lr_rot)
     if args.resume:
         model_params, it0 = torch.load(args.resume, map_location=dev, weights_only=False)
         scene.restore(model_params, opt)
@@ -128,6 +136,11 @@ def run(args) -> dict:
         bp = os.path.join(os.path.dirname(os.path.abspath(args.resume)), f"boxes{int(it0)}.pth")
         if box_poses is not None and os.path.exists(bp):
             box_poses.load_state_dict(torch.load(bp, map_location=dev, weights_only=False))
+        tp = os.path.join(os.path.dirname(os.path.abspath(args.resume)), f"actor_twists{int(it0)}.pth")
+        if actor_twists is not None and os.path.exists(tp):
+            actor_twists.load_state_dict(torch.load(tp, map_location=dev, weights_only=False))
+        elif actor_twists is not None and rank == 0:                  # a checkpoint written without the switch, or copied without its sibling file
+            print(f"[train] warning: --refine-actor-twist resumes from {args.resume} but {tp} is missing: the twists start from the boxes again", file=sys.stderr, flush=True)
     os.makedirs(args.out, exist_ok=True)
     bg = torch.tensor([0.0, 0.0, 1.0], device=dev)       # the reference's background for (intensity, ray-hit, ray-drop): train.py:106
     log, t0 = [], time.perf_counter()
@@ -138,8 +151,12 @@ def run(args) -> dict:
     for it in range(first, (first - 1 if only_refine else args.iters) + 1):
         torch.manual_seed(args.seed * 1_000_003 + it)      # the densification's random draws: a function of (seed, iteration) on every rank
         frame = frame_of(args.seed, it, seq.train_frames)
+        if actor_twists is not None:
+            actor_twists.zero_grad()
         res = training.training_step(scene, seq.frames, frame, it, opt, bg, dynamic=bool(seq.meta.get("dynamic")), poses=sensor_poses,
                                       box_poses=box_poses, chamfer_points_detached=not args.chamfer_grad)
+        if actor_twists is not None:
+            actor_twists.step()
         if it % args.log_every == 0 or it == args.iters:
             row = {"iteration": it, "frame": int(frame), "loss": float(res["loss"]), "depth": float(res["depth"]), "intensity": float(res["intensity"]),
                    "raydrop": float(res["raydrop"]), "points": int(res["points"]), "seconds": round(time.perf_counter() - t0, 3)}
@@ -152,6 +169,8 @@ def run(args) -> dict:
                 torch.save(sensor_poses.state_dict(), os.path.join(args.out, f"poses{it}.pth"))
             if box_poses is not None:
                 torch.save(box_poses.state_dict(), os.path.join(args.out, f"boxes{it}.pth"))
+            if actor_twists is not None:
+                torch.save(actor_twists.state_dict(), os.path.join(args.out, f"actor_twists{it}.pth"))
     if renderer.sharded is not None:
         renderer.sharded.check(wait=True)
     elif renderer.tracer_2dgs is not None:
@@ -164,7 +183,7 @@ def run(args) -> dict:
     if world > 1:
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()
-    return {"log": log, "scene": scene, "sequence": seq, "last": res, "poses": sensor_poses, "boxes": box_poses, "unet": unet}
+    return {"log": log, "scene": scene, "sequence": seq, "last": res, "poses": sensor_poses, "boxes": box_poses, "unet": unet, "actor_twists": actor_twists}
 
 
 def main(argv=None) -> int:
@@ -222,6 +241,13 @@ def main(argv=None) -> int:
     ap.add_argument("--refine-twist", action="store_true", help="also learn every frame's twist; needs --refine-poses and a --sweep")
     ap.add_argument("--twist-lr-trans", type=float, default=1e-3, help="--refine-twist: Adam learning rate of the twists' translation part (m per sweep)")
     ap.add_argument("--twist-lr-rot", type=float, default=1e-4, help="--refine-twist: Adam learning rate of the twists' rotation part (rad per sweep)")
+    ap.add_argument("--actor-sweep", choices=("off", "stored", "boxes"), default="off", help="the actors move within a sweep too: every Gaussian of an actor is placed where "
+                    "it is when the sweep passes over it (lidar_rt_amd.actor_sweep); needs a --sweep.  stored: the twists of the box file; boxes: twists derived from "
+                    "consecutive tracking boxes (with --sweep-fraction); off (the default): every actor at its box pose of the reference instant")
+    ap.add_argument("--refine-actor-twist", action="store_true", help="also learn every (actor, frame) twist; needs --actor-sweep; written as actor_twists<it>.pth beside "
+                    "each checkpoint and read back by --resume")
+    ap.add_argument("--actor-twist-lr-trans", type=float, default=1e-3, help="--refine-actor-twist: Adam learning rate of the translation part (m per sweep)")
+    ap.add_argument("--actor-twist-lr-rot", type=float, default=1e-4, help="--refine-actor-twist: Adam learning rate of the rotation part (rad per sweep)")
     ap.add_argument("--refine-boxes", action="store_true", help="also learn a per-frame se(3) correction of every actor's tracking box through the "
                     "pose-table gradient of the fused pre-processing (lidar_rt_amd.actor_poses); written as boxes<it>.pth beside each checkpoint and "
                     "read back by --resume; works with --gpus N")
@@ -253,6 +279,12 @@ def main(argv=None) -> int:
         ap.error("--refine-twist needs --refine-poses (the twists are learnt beside the pose corrections)")
     if args.refine_twist and args.sweep == "off":
         ap.error("--refine-twist needs a sweep (--sweep stored or --sweep poses): without one a frame has no twist")
+    if args.actor_sweep != "off" and args.sweep == "off":
+        ap.error("--actor-sweep needs a sweep (--sweep stored or --sweep poses): the instants are those of the sensor's columns")
+    if args.refine_actor_twist and args.actor_sweep == "off":
+        ap.error("--refine-actor-twist needs --actor-sweep stored or boxes: without one an actor has no twist")
+    if args.refine_actor_twist and args.gpus > 1:
+        ap.error("--refine-actor-twist is refused with --gpus > 1, as --refine-twist is")
     if args.exact_accum and args.deterministic:
         ap.error("--deterministic takes the hit weights from the backward (the forward's are float atomics): not with --exact-accum")
     if args.out is None:

@@ -31,25 +31,47 @@ class _GT:
         self.xyz, self.sc, self.rot, self.op, self.sh = t(sc["means"]), t(sc["scales"]), t(sc["rotations"]), t(sc["opacities"]), t(sc["shs"])
         self.active_sh_degree, self.bounding_box = 3, box
         self.get_scaling, self.get_opacity, self.get_features = self.sc, self.op, self.sh
+        self.motion, self._swept = {}, {}          # --actor-sweep: frame -> the sensor's (sensor2world, twist, tau, data_type, sensor2ego); frame -> (xyz_s, rot_s)
 
+    def _local(self, ts):
+        """The actor-local centres and raw rotations of frame ``ts``: advanced to every Gaussian's own instant (lidar_rt_amd.actor_sweep) where the
+        frame has a moving sensor and the box a twist, the fixed ones otherwise."""
+        tw = getattr(self.bounding_box, "twist", {}).get(ts) if self._pose(ts) is not None else None
+        if tw is None or ts not in self.motion:
+            return self.xyz, self.rot
+        if ts not in self._swept:
+            from lidar_rt_amd.actor_sweep import actor_sweep
+            from lidar_rt_amd.preprocess import pack_poses
+            ps = self._pose(ts)
+            seg, tab = pack_poses([(ps[0], ps[1])], [self.xyz.shape[0]], self.xyz.device)
+            s2w, xi, tau, data_type, s2e = self.motion[ts]
+            with torch.no_grad():
+                xyz_s, rot_s, _ = actor_sweep(self.xyz, self.rot, seg, tab, tw.reshape(1, 6).to(self.xyz.device, torch.float32), s2w, xi, tau, int(tau.numel()), data_type, s2e)
+            self._swept = {ts: (xyz_s, rot_s)}
+        return self._swept[ts]
     def _pose(self, ts):
         return self.bounding_box.frame[ts] if (self.bounding_box is not None and ts in self.bounding_box.frame) else None
 
     def get_rotation(self, ts=0.0):
         ps = self._pose(ts)
-        return (ps[1] if ps is not None else torch.zeros((1, 4), device=self.xyz.device)), torch.nn.functional.normalize(self.rot)
+        return (ps[1] if ps is not None else torch.zeros((1, 4), device=self.xyz.device)), torch.nn.functional.normalize(self._local(ts)[1])
 
     def get_world_xyz(self, ts=0.0):
         from lidar_rt_amd.training import _rotation_matrix
         ps = self._pose(ts)
-        return self.xyz if ps is None else self.xyz @ _rotation_matrix(ps[1].reshape(1, 4)).squeeze(0).T + ps[0]
+        return self.xyz if ps is None else self._local(ts)[0] @ _rotation_matrix(ps[1].reshape(1, 4)).squeeze(0).T + ps[0]
 
 
-def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0", test_every: int = 0, sweep_speed: float = 0.0, hw=None):
-    """``sweep_speed`` V != 0: the sensor moves while it turns -- V metres forward (its x axis) and 0.01 V rad of yaw per sweep; the ground truth is
+def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0", test_every: int = 0, sweep_speed: float = 0.0, hw=None, actor_sweep: bool = False):
+    """``actor_sweep`` (with ``sweep_speed``): the actors move within a sweep too -- their twists are those of their tracking boxes
+    (``actor_twists_from_boxes``, one sweep per frame id), every Gaussian of an actor is rendered where it is when the sweep passes over it
+    (lidar_rt_amd.actor_sweep) and the box file stores the twists (train / evaluate / simulate --actor-sweep stored).
+    ``sweep_speed`` V != 0: the sensor moves while it turns -- V metres forward (its x axis) and 0.01 V rad of yaw per sweep; the ground truth is
     rendered with sweep rays (lidar_rt_amd.sweep: one pose per column, the frame's pose at mid-sweep) and every frame stores its twist.
     ``hw``: another image size than the dataset's (tests)."""
     dev = torch.device(device)
+    if actor_sweep and not sweep_speed:
+        raise SystemExit("--actor-sweep needs --sweep-speed: the instants are those of a moving sensor's columns")
     twist = None if not sweep_speed else np.array([sweep_speed, 0.0, 0.0, 0.0, 0.0, 0.01 * sweep_speed], np.float32)
     n = lambda x: max(int(x * scale), 64)
     boxes, actors = None, []
@@ -88,6 +110,14 @@ def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0
             for k, f in enumerate(boxes["frames"]):
                 tb.frame[f] = (torch.as_tensor(boxes["translation"][a, k], device=dev), torch.as_tensor(boxes["quaternion"][a, k], device=dev).reshape(1, 4), None, None)
             tbs.append(tb)
+        if actor_sweep:
+            from lidar_rt_amd.actor_sweep import actor_twists_from_boxes
+            eta = actor_twists_from_boxes(tbs, boxes["frames"])
+            boxes["twist"] = np.stack([[eta[a][f] for f in boxes["frames"]] for a in range(len(tbs))]).astype(np.float32)
+            for a, tb in enumerate(tbs):
+                tb.twist = {f: torch.as_tensor(boxes["twist"][a, k], device=dev) for k, f in enumerate(boxes["frames"])}
+    elif actor_sweep:
+        raise SystemExit(f"--actor-sweep: shape {shape} has no actors")
     assets = [_GT(bg, dev)] + [_GT(a_, dev, tb) for a_, tb in zip(actors, tbs)]
     args = types.SimpleNamespace(dynamic=boxes is not None, opt=types.SimpleNamespace(use_rayhit=True), pipe=types.SimpleNamespace())      # ray-drop = softmax([hit, drop]): a return where the accumulated weight exceeds the final transmittance
     from lidar_rt_amd.training import RangeFrames
@@ -105,6 +135,10 @@ def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0
                     from lidar_rt_amd import sweep
                     o, d = sweep.sweep_rays(s2w.to(torch.float32), torch.as_tensor(twist, device=dev), H, W, inc_f, data_type,
                                             None if s2e is None else torch.as_tensor(s2e, dtype=torch.float32))
+                    if actor_sweep:                              # the columns' instants and poses the rays above were made with
+                        for g in assets[1:]:
+                            g.motion[f] = (s2w.to(torch.float32), torch.as_tensor(twist, device=dev), sweep.column_times(W).to(torch.float32), data_type,
+                                           None if s2e is None else torch.as_tensor(s2e, dtype=torch.float32))
                 renderer.tracer_2dgs = renderer.tracer_2dgs or renderer.Tracer()
                 renderer.tracer_2dgs.eval()
                 pkg = renderer.raytracing(f, assets, (o, d, o[0, 0]), torch.tensor([0.0, 0.0, 1.0]), args)
@@ -127,6 +161,8 @@ if __name__ == "__main__":
     ap.add_argument("--test-every", type=int, default=0)
     ap.add_argument("--sweep-speed", type=float, default=0.0, metavar="V", help="a moving sensor: V metres forward and 0.01 V rad of yaw per sweep; the ground truth "
                     "is rendered with sweep rays and the twists are stored (train / evaluate --sweep stored)")
+    ap.add_argument("--actor-sweep", action="store_true", help="with --sweep-speed: the actors move within a sweep too; the ground truth is rendered through "
+                    "lidar_rt_amd.actor_sweep with the twists of the tracking boxes, and the box file stores them (train / evaluate / simulate --actor-sweep stored)")
     ap.add_argument("--hw", type=int, nargs=2, default=None, metavar=("H", "W"), help="another image size than the dataset's")
     a = ap.parse_args()
-    print(make(a.shape, a.out, a.frames, a.scale, test_every=a.test_every, sweep_speed=a.sweep_speed, hw=tuple(a.hw) if a.hw else None))
+    print(make(a.shape, a.out, a.frames, a.scale, test_every=a.test_every, sweep_speed=a.sweep_speed, hw=tuple(a.hw) if a.hw else None, actor_sweep=a.actor_sweep))
