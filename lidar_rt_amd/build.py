@@ -45,6 +45,9 @@
 * ``csrc/liblrt_actorsweep.so`` -- actors that move within a sweep (``csrc/lrt_actorsweep.hip``, C ABI ``include/lrt_actorsweep.h``): a thirteenth
   product library on the same pattern.  Loaded by ``lidar_rt_amd.actor_sweep``.
 
+* ``csrc/liblrt_beams.so`` -- the beam rays: the sweep rays with per-beam elevation and azimuth offsets, and their pose, twist and table gradients
+  (``csrc/lrt_beams.hip``, C ABI ``include/lrt_beams.h``): a fourteenth product library on the same pattern.  Loaded by ``lidar_rt_amd.beams``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -139,6 +142,12 @@ ACTORSWEEP_STAMP = os.path.join(CSRC, "liblrt_actorsweep.srchash")
 ACTORSWEEP_SOURCES = ["lrt_actorsweep.hip"]
 ACTORSWEEP_HEADERS = ["lrt_actorsweep_math.h", "lrt_sweepproj_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h",
                       os.path.join("..", "..", "include", "lrt_actorsweep.h")]
+# the beam-ray library: once more (it reads the sweep rays' rule header and ABI constants; their hashes do not read back)
+BEAMS_LIB = os.path.join(CSRC, "liblrt_beams.so")
+BEAMS_STAMP = os.path.join(CSRC, "liblrt_beams.srchash")
+BEAMS_SOURCES = ["lrt_beams.hip"]
+BEAMS_HEADERS = ["lrt_beams_math.h", "lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_beams.h"),
+                 os.path.join("..", "..", "include", "lrt_sweep.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -647,6 +656,46 @@ def build_actorsweep(force: bool = False, verbose: bool = False) -> str:
     return ACTORSWEEP_LIB
 
 
+def beams_source_hash() -> str:
+    """source_hash() of the beam-ray library: over ITS sources, headers (the sweep rays' rule header included) and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(BEAMS_SOURCES + BEAMS_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def beams_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(BEAMS_LIB):
+        return True
+    try:
+        return open(BEAMS_STAMP).read().strip() != beams_source_hash()
+    except OSError:
+        return True
+
+
+def build_beams(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_beams.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other thirteen libraries."""
+    if force or beams_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", BEAMS_LIB] \
+            + [os.path.join(CSRC, s) for s in BEAMS_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(BEAMS_STAMP, "w") as f:
+            f.write(beams_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(BEAMS_LIB)} is up to date (sources {beams_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(BEAMS_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return BEAMS_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -754,6 +803,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_sweepproj(force, verbose)
     build_unproject(force, verbose)
     build_actorsweep(force, verbose)
+    build_beams(force, verbose)
     return lib
 
 

@@ -39,6 +39,11 @@ def run(args) -> dict:
         if getattr(args, "actor_twists", None):
             for (a, f), v in torch.load(args.actor_twists, map_location=dev, weights_only=False)["eta"].items():
                 seq.boxes[a].twist[f] = v.to(dev)
+    if getattr(args, "beams", None):
+        # the sensor's beam table (lidar_rt_amd.beams): what python -m lidar_rt_amd.train --refine-beams learnt, or a text table; every frame renders through it
+        from . import beams as beams_mod
+        rows = int(next(iter(seq.frames.depth.values())).shape[0])
+        beams_mod.apply_table(seq.frames, beams_mod.load_table(args.beams, rows, dev))
     opt = training.default_options()
     scene = sequence.scene_from_sequence(seq, max_points=args.max_points, seed=args.seed)
     scene.training_setup(opt)
@@ -110,6 +115,8 @@ def main(argv=None) -> int:
     ap.add_argument("--actor-sweep", choices=("off", "stored", "boxes"), default="off", help="the actors move within a sweep too (lidar_rt_amd.actor_sweep), as "
                     "python -m lidar_rt_amd.train --actor-sweep; needs a --sweep")
     ap.add_argument("--actor-twists", default=None, help="--actor-sweep: learnt twists (actor_twists<it>.pth of python -m lidar_rt_amd.train --refine-actor-twist)")
+    ap.add_argument("--beams", default=None, metavar="FILE", help="render through a beam table (lidar_rt_amd.beams): a beams<it>.pth of python -m lidar_rt_amd.train "
+                    "--refine-beams, or a text table with one `eps delta` pair per image row (rad)")
     ap.add_argument("--out", default=None, help="also write the JSON object to this file")
     args = ap.parse_args(argv)
     if args.actor_sweep != "off" and args.sweep == "off":

@@ -361,7 +361,7 @@ def simulate(data: str, ckpt: str, out: str, frames: str = "test", max_frames: i
              poses: Optional[str] = None, remove_actor: Sequence[int] = (), move_actor: Sequence[Sequence[float]] = (), only: Optional[str] = None,
              frame: str = "world", fmt: str = "bin", fields: str = "xyzi", sequence_dir: Optional[str] = None, backend: Optional[str] = None,
              min_depth: float = 0.0, max_depth: Optional[float] = None, max_points: int = 2_000_000, seed: int = 0, device: int = 0,
-             origin_shift: bool = True, actor_sweep: str = "off", actor_twists: Optional[str] = None) -> dict:
+             origin_shift: bool = True, actor_sweep: str = "off", actor_twists: Optional[str] = None, beams: Optional[str] = None) -> dict:
     """The run behind the command (see the module text); returns what ``OUT/simulate.json`` holds.  ``origin_shift=False``: the tables of a moving
     sensor are the plain inverses of pose, twist and ``tau`` (``column_transforms`` without ``origins``)."""
     from . import evaluate as evaluate_mod
@@ -417,6 +417,14 @@ def simulate(data: str, ckpt: str, out: str, frames: str = "test", max_frames: i
     new_poses = ingest.read_poses(poses, sorted(int(f) for f in seq.frames.rays)) if poses else None
     assets, decomp, edits = apply_edits(scene.gaussians_assets, remove_actor, move_actor, only)
     sensor = build_sensor(seq, ids, height, width, inclination, mount, new_poses, sweep_ref, sweep_direction, sweep_fraction)
+    if beams:
+        # the sensor's beam table (lidar_rt_amd.beams), one (eps, delta) pair per row of the SIMULATED sensor; the origins stay one per column
+        from . import beams as beams_mod
+        rows = int(sensor.depth[ids[0]].shape[0])
+        try:
+            beams_mod.apply_table(sensor, beams_mod.load_table(beams, rows, dev), ids)
+        except beams_mod.BeamError as e:
+            raise SimulateError(f"simulate: --beams: {e}") from None
     bg = torch.tensor([0.0, 0.0, 1.0], device=dev)
     rargs = SimpleNamespace(dynamic=bool(seq.meta.get("dynamic")), opt=SimpleNamespace(use_rayhit=bool(getattr(opt, "use_rayhit", False))), pipe=SimpleNamespace())
     from . import renderer
@@ -441,7 +449,7 @@ def simulate(data: str, ckpt: str, out: str, frames: str = "test", max_frames: i
                             "sweep": sweep, "sweep_ref": sweep_ref, "sweep_direction": sweep_direction, "sweep_fraction": sweep_fraction, "height": height,
                             "width": width, "inclination": inclination, "mount": None if mount is None else [float(x) for x in mount], "poses": poses,
                             "min_depth": min_depth, "max_depth": max_depth, "backend": backend, "origin_shift": bool(origin_shift),
-                            "actor_sweep": actor_sweep, "actor_twists": actor_twists},
+                            "actor_sweep": actor_sweep, "actor_twists": actor_twists, **({"beams": beams} if beams else {})},
               **({"twists": {str(f): [float(x) for x in sw[f][0]] for f in sw}, "tau": {str(f): [float(x) for x in sw[f][1]] for f in sw}} if sw else {})}
     with open(os.path.join(out, "simulate.json"), "w") as fh:
         json.dump(report, fh, indent=1)
@@ -485,6 +493,8 @@ def main(argv=None) -> int:
     ap.add_argument("--actor-sweep", choices=("off", "stored", "boxes"), default="off", help="the actors move within a sweep too (lidar_rt_amd.actor_sweep), as "
                     "python -m lidar_rt_amd.evaluate --actor-sweep; needs a --sweep.  --move-actor keeps an actor's twist: it is a motion in the actor's own frame")
     ap.add_argument("--actor-twists", default=None, help="--actor-sweep: learnt twists (actor_twists<it>.pth of python -m lidar_rt_amd.train --refine-actor-twist)")
+    ap.add_argument("--beams", default=None, metavar="FILE", help="a beam table of the simulated sensor (lidar_rt_amd.beams): a beams<it>.pth of python -m "
+                    "lidar_rt_amd.train --refine-beams, or a text table with one `eps delta` pair per image row (rad)")
     ap.add_argument("--height", type=int, default=None, help="rows of the simulated sensor (default: the sequence's)")
     ap.add_argument("--width", type=int, default=None, help="columns of the simulated sensor (default: the sequence's)")
     g = ap.add_mutually_exclusive_group()

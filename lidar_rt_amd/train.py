@@ -105,13 +105,28 @@ def run(args) -> dict:
     scene.training_setup(opt)
     first = 1
     sensor_poses = None
+    beam_cal = None
+    beam_table = None
+    if getattr(args, "refine_beams", False) or getattr(args, "beams", None):
+        # the sensor's beam table (lidar_rt_amd.beams): learnt through the ray gradients (--refine-beams), or read from a file and held fixed (--beams alone)
+        from . import beams as beams_mod
+        rows = int(seq.frames.depth[seq.train_frames[0]].shape[0])
+        init = beams_mod.load_table(args.beams, rows, dev) if getattr(args, "beams", None) else None
+        if getattr(args, "refine_beams", False):
+            # a uniform azimuth offset is a yaw of the sensor: beside --refine-poses the table's azimuth column is kept at zero mean
+            beam_cal = beams_mod.BeamCalibration(rows, init=init, lr=getattr(args, "beam_lr", 1e-4), zero_mean_azimuth=bool(args.refine_poses), device=dev)
+        else:
+            beam_table = init
+        if not args.refine_poses:
+            from .poses import SensorPoses
+            sensor_poses = SensorPoses(seq.frames, seq.train_frames, beams=beam_cal if beam_cal is not None else beam_table, fixed_poses=True)
     if args.refine_poses:
         # one se(3) correction per training frame, learnt through the tracer's ray gradients (lidar_rt_amd.poses); saved beside each checkpoint
         from .poses import SensorPoses
         # --refine-twist: a moving sensor's twists are parameters too (frames loaded with --sweep carry them)
         sensor_poses = SensorPoses(seq.frames, seq.train_frames, lr_trans=args.pose_lr_trans, lr_rot=args.pose_lr_rot,
                                    refine_twist=bool(getattr(args, "refine_twist", False)), lr_twist_trans=getattr(args, "twist_lr_trans", None),
-                                   lr_twist_rot=getattr(args, "twist_lr_rot", None))
+                                   lr_twist_rot=getattr(args, "twist_lr_rot", None), beams=beam_cal if beam_cal is not None else beam_table)
     box_poses = None
     if args.refine_boxes:
         # one se(3) correction per (actor, training frame) with a box, learnt through the pose-table gradient of the fused pre-processing
@@ -133,6 +148,15 @@ def run(args) -> dict:
         pp = os.path.join(os.path.dirname(os.path.abspath(args.resume)), f"poses{int(it0)}.pth")
         if sensor_poses is not None and os.path.exists(pp):
             sensor_poses.load_state_dict(torch.load(pp, map_location=dev, weights_only=False))
+        mp = os.path.join(os.path.dirname(os.path.abspath(args.resume)), f"beams{int(it0)}.pth")
+        if beam_cal is not None and os.path.exists(mp):
+            beam_cal.load(mp)
+            if rank == 0:
+                import hashlib
+                print(json.dumps({"beams_resumed": mp, "sha256": hashlib.sha256(beam_cal.table.detach().cpu().numpy().tobytes()).hexdigest()}), flush=True)
+        elif beam_cal is not None and rank == 0:                      # a checkpoint written without the switch, or copied without its sibling file
+            print(f"[train] warning: --refine-beams resumes from {args.resume} but {mp} is missing: the table starts from "
+                  f"{'--beams ' + args.beams if getattr(args, 'beams', None) else 'zero'} again", file=sys.stderr, flush=True)
         bp = os.path.join(os.path.dirname(os.path.abspath(args.resume)), f"boxes{int(it0)}.pth")
         if box_poses is not None and os.path.exists(bp):
             box_poses.load_state_dict(torch.load(bp, map_location=dev, weights_only=False))
@@ -165,8 +189,10 @@ def run(args) -> dict:
                 print(json.dumps(row), flush=True)
         if rank == 0 and (it % args.save_every == 0 or it == args.iters):
             scene.save(it, os.path.join(args.out, f"chkpnt{it}.pth"))
-            if sensor_poses is not None:
+            if sensor_poses is not None and args.refine_poses:
                 torch.save(sensor_poses.state_dict(), os.path.join(args.out, f"poses{it}.pth"))
+            if beam_cal is not None:
+                beam_cal.save(os.path.join(args.out, f"beams{it}.pth"))
             if box_poses is not None:
                 torch.save(box_poses.state_dict(), os.path.join(args.out, f"boxes{it}.pth"))
             if actor_twists is not None:
@@ -183,7 +209,7 @@ def run(args) -> dict:
     if world > 1:
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()
-    return {"log": log, "scene": scene, "sequence": seq, "last": res, "poses": sensor_poses, "boxes": box_poses, "unet": unet, "actor_twists": actor_twists}
+    return {"log": log, "scene": scene, "sequence": seq, "last": res, "poses": sensor_poses, "boxes": box_poses, "unet": unet, "actor_twists": actor_twists, "beams": beam_cal}
 
 
 def main(argv=None) -> int:
@@ -241,6 +267,12 @@ def main(argv=None) -> int:
     ap.add_argument("--refine-twist", action="store_true", help="also learn every frame's twist; needs --refine-poses and a --sweep")
     ap.add_argument("--twist-lr-trans", type=float, default=1e-3, help="--refine-twist: Adam learning rate of the twists' translation part (m per sweep)")
     ap.add_argument("--twist-lr-rot", type=float, default=1e-4, help="--refine-twist: Adam learning rate of the twists' rotation part (rad per sweep)")
+    ap.add_argument("--refine-beams", action="store_true", help="also learn the sensor's beam table -- an elevation and an azimuth offset per image row "
+                    "(lidar_rt_amd.beams) -- through the tracer's ray gradients; alone (the recorded poses held fixed) or beside --refine-poses (the azimuth column "
+                    "then keeps a zero mean: a uniform azimuth offset is a yaw); written as beams<it>.pth beside each checkpoint and read back by --resume")
+    ap.add_argument("--beam-lr", type=float, default=1e-4, help="--refine-beams: Adam learning rate of the offsets (rad)")
+    ap.add_argument("--beams", default=None, help="a beam table to start from (--refine-beams) or to render through as it is: a beams<it>.pth, or a text table with "
+                    "one `eps delta` pair per image row (rad)")
     ap.add_argument("--actor-sweep", choices=("off", "stored", "boxes"), default="off", help="the actors move within a sweep too: every Gaussian of an actor is placed where "
                     "it is when the sweep passes over it (lidar_rt_amd.actor_sweep); needs a --sweep.  stored: the twists of the box file; boxes: twists derived from "
                     "consecutive tracking boxes (with --sweep-fraction); off (the default): every actor at its box pose of the reference instant")
@@ -275,6 +307,11 @@ def main(argv=None) -> int:
         ap.error("--voxel-size must be positive")
     if args.refine_poses and args.gpus > 1:
         ap.error("--refine-poses needs ray gradients, which azimuth sharding (--gpus > 1) does not provide")
+    if (args.refine_beams or args.beams) and args.gpus > 1:
+        ap.error("--refine-beams / --beams are refused with --gpus > 1, as --refine-poses is: the rays of a beam table come from the sensor model, "
+                 "which azimuth sharding (--gpus > 1) does not provide")
+    if not args.beam_lr > 0:
+        ap.error("--beam-lr must be positive")
     if args.refine_twist and not args.refine_poses:               # so --refine-twist is refused with --gpus > 1 too: --refine-poses is, above
         ap.error("--refine-twist needs --refine-poses (the twists are learnt beside the pose corrections)")
     if args.refine_twist and args.sweep == "off":

@@ -62,17 +62,8 @@ class _GT:
         return self.xyz if ps is None else self._local(ts)[0] @ _rotation_matrix(ps[1].reshape(1, 4)).squeeze(0).T + ps[0]
 
 
-def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0", test_every: int = 0, sweep_speed: float = 0.0, hw=None, actor_sweep: bool = False):
-    """``actor_sweep`` (with ``sweep_speed``): the actors move within a sweep too -- their twists are those of their tracking boxes
-    (``actor_twists_from_boxes``, one sweep per frame id), every Gaussian of an actor is rendered where it is when the sweep passes over it
-    (lidar_rt_amd.actor_sweep) and the box file stores the twists (train / evaluate / simulate --actor-sweep stored).
-    ``sweep_speed`` V != 0: the sensor moves while it turns -- V metres forward (its x axis) and 0.01 V rad of yaw per sweep; the ground truth is
-    rendered with sweep rays (lidar_rt_amd.sweep: one pose per column, the frame's pose at mid-sweep) and every frame stores its twist.
-    ``hw``: another image size than the dataset's (tests)."""
-    dev = torch.device(device)
-    if actor_sweep and not sweep_speed:
-        raise SystemExit("--actor-sweep needs --sweep-speed: the instants are those of a moving sensor's columns")
-    twist = None if not sweep_speed else np.array([sweep_speed, 0.0, 0.0, 0.0, 0.0, 0.01 * sweep_speed], np.float32)
+def _ground_truth(shape: str, n_frames: int, scale: float, dev, hw=None, actor_sweep: bool = False):
+    """The scene a sequence is rendered from: its sensor (H, W, data_type, s2e, inc, pose_s), the tracking boxes, and the ground-truth assets."""
     n = lambda x: max(int(x * scale), 64)
     boxes, actors = None, []
     if shape == "kitti360_dynamic":
@@ -120,21 +111,68 @@ def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0
         raise SystemExit(f"--actor-sweep: shape {shape} has no actors")
     assets = [_GT(bg, dev)] + [_GT(a_, dev, tb) for a_, tb in zip(actors, tbs)]
     args = types.SimpleNamespace(dynamic=boxes is not None, opt=types.SimpleNamespace(use_rayhit=True), pipe=types.SimpleNamespace())      # ray-drop = softmax([hit, drop]): a return where the accumulated weight exceeds the final transmittance
+    return types.SimpleNamespace(H=H, W=W, data_type=data_type, s2e=s2e, inc=inc, pose_s=pose_s, boxes=boxes, bg=bg, assets=assets, args=args)
+
+
+def render_ground_truth(shape: str, frame: int, rays, n_frames: int, scale: float = 1.0, device="cuda:0", hw=None):
+    """(H, W) depth of the ground-truth scene of ``make(shape, ..., n_frames, scale)`` at ``frame`` along the given rays ``(o, d)``: what the sensor
+    of those rays would have measured (a test renders a sequence's frame again through another beam table)."""
+    dev = torch.device(device)
+    g = _ground_truth(shape, n_frames, scale, dev, hw)
+    old = renderer.tracer_2dgs, renderer.use_fused_preprocess, renderer.deferred_accum
+    renderer.tracer_2dgs, renderer.use_fused_preprocess, renderer.deferred_accum = None, False, False
+    try:
+        with torch.no_grad():
+            renderer.tracer_2dgs = renderer.Tracer()
+            renderer.tracer_2dgs.eval()
+            o, d = rays
+            pkg = renderer.raytracing(frame, g.assets, (o, d, o[0, 0]), torch.tensor([0.0, 0.0, 1.0]), g.args)
+            return pkg["depth"].squeeze(-1)
+    finally:
+        renderer.tracer_2dgs, renderer.use_fused_preprocess, renderer.deferred_accum = old
+
+
+def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0", test_every: int = 0, sweep_speed: float = 0.0, hw=None, actor_sweep: bool = False,
+         beam_error: float = 0.0):
+    """``beam_error`` SIGMA != 0: the sensor's lasers are not where the nominal grid puts them -- the ground truth is rendered through
+    ``lidar_rt_amd.beams.beam_rays`` with a seeded (H, 2) table of elevation and azimuth offsets of that standard deviation [rad]; the stored
+    inclination stays nominal and the true table is written as ``beams_true.npy`` into the sequence directory.
+    ``actor_sweep`` (with ``sweep_speed``): the actors move within a sweep too -- their twists are those of their tracking boxes
+    (``actor_twists_from_boxes``, one sweep per frame id), every Gaussian of an actor is rendered where it is when the sweep passes over it
+    (lidar_rt_amd.actor_sweep) and the box file stores the twists (train / evaluate / simulate --actor-sweep stored).
+    ``sweep_speed`` V != 0: the sensor moves while it turns -- V metres forward (its x axis) and 0.01 V rad of yaw per sweep; the ground truth is
+    rendered with sweep rays (lidar_rt_amd.sweep: one pose per column, the frame's pose at mid-sweep) and every frame stores its twist.
+    ``hw``: another image size than the dataset's (tests)."""
+    dev = torch.device(device)
+    if actor_sweep and not sweep_speed:
+        raise SystemExit("--actor-sweep needs --sweep-speed: the instants are those of a moving sensor's columns")
+    twist = None if not sweep_speed else np.array([sweep_speed, 0.0, 0.0, 0.0, 0.0, 0.01 * sweep_speed], np.float32)
+    g = _ground_truth(shape, n_frames, scale, dev, hw, actor_sweep)
+    H, W, data_type, s2e, inc, pose_s, boxes, bg, assets, args = g.H, g.W, g.data_type, g.s2e, g.inc, g.pose_s, g.boxes, g.bg, g.assets, g.args
     from lidar_rt_amd.training import RangeFrames
     old = renderer.tracer_2dgs, renderer.use_fused_preprocess, renderer.deferred_accum
     renderer.tracer_2dgs, renderer.use_fused_preprocess, renderer.deferred_accum = None, False, False
     frames = []
+    beams_true = None
+    if beam_error:
+        beams_true = torch.as_tensor(np.random.default_rng(scenes.SEED + 29).normal(0.0, float(beam_error), size=(H, 2)).astype(np.float32), device=dev)
     try:
         with torch.no_grad():
             for f in range(n_frames):
                 s2w = torch.as_tensor(pose_s(f), device=dev)
                 inc_f = [float(x) for x in inc] if len(inc) > 2 else (float(inc[0]), float(inc[1]))
-                if twist is None:
+                if beams_true is not None:                       # the sensor as it is built; what is stored below is the nominal grid
+                    from lidar_rt_amd import beams as beams_mod
+                    o, d = beams_mod.beam_rays(s2w.to(torch.float32), None if twist is None else torch.as_tensor(twist, device=dev), H, W, inc_f, beams_true,
+                                               data_type, None if s2e is None else torch.as_tensor(s2e, dtype=torch.float32))
+                elif twist is None:
                     o, d = RangeFrames.range_rays(H, W, inc_f, s2w, data_type, None if s2e is None else torch.as_tensor(s2e, device=dev))
                 else:
                     from lidar_rt_amd import sweep
                     o, d = sweep.sweep_rays(s2w.to(torch.float32), torch.as_tensor(twist, device=dev), H, W, inc_f, data_type,
                                             None if s2e is None else torch.as_tensor(s2e, dtype=torch.float32))
+                if twist is not None:
+                    from lidar_rt_amd import sweep
                     if actor_sweep:                              # the columns' instants and poses the rays above were made with
                         for g in assets[1:]:
                             g.motion[f] = (s2w.to(torch.float32), torch.as_tensor(twist, device=dev), sweep.column_times(W).to(torch.float32), data_type,
@@ -149,7 +187,10 @@ def make(shape: str, out: str, n_frames: int, scale: float = 1.0, device="cuda:0
     finally:
         renderer.tracer_2dgs, renderer.use_fused_preprocess, renderer.deferred_accum = old
     test = [f for f in range(n_frames) if test_every and f % test_every == test_every - 1]
-    return sequence.write_sequence(out, frames, data_type=data_type, extent=float(np.abs(bg["means"]).max()), sensor2ego=s2e, boxes=boxes, test_frames=test)
+    meta = sequence.write_sequence(out, frames, data_type=data_type, extent=float(np.abs(bg["means"]).max()), sensor2ego=s2e, boxes=boxes, test_frames=test)
+    if beams_true is not None:
+        np.save(os.path.join(out, "beams_true.npy"), beams_true.cpu().numpy())
+    return meta
 
 
 if __name__ == "__main__":
@@ -163,6 +204,8 @@ if __name__ == "__main__":
                     "is rendered with sweep rays and the twists are stored (train / evaluate --sweep stored)")
     ap.add_argument("--actor-sweep", action="store_true", help="with --sweep-speed: the actors move within a sweep too; the ground truth is rendered through "
                     "lidar_rt_amd.actor_sweep with the twists of the tracking boxes, and the box file stores them (train / evaluate / simulate --actor-sweep stored)")
+    ap.add_argument("--beam-error", type=float, default=0.0, metavar="SIGMA", help="per-beam elevation and azimuth offsets of that standard deviation [rad]: the ground "
+                    "truth is rendered through lidar_rt_amd.beams with a seeded table, written as beams_true.npy; the stored inclination stays nominal")
     ap.add_argument("--hw", type=int, nargs=2, default=None, metavar=("H", "W"), help="another image size than the dataset's")
     a = ap.parse_args()
-    print(make(a.shape, a.out, a.frames, a.scale, test_every=a.test_every, sweep_speed=a.sweep_speed, hw=tuple(a.hw) if a.hw else None, actor_sweep=a.actor_sweep))
+    print(make(a.shape, a.out, a.frames, a.scale, test_every=a.test_every, sweep_speed=a.sweep_speed, hw=tuple(a.hw) if a.hw else None, actor_sweep=a.actor_sweep, beam_error=a.beam_error))
