@@ -48,6 +48,9 @@
 * ``csrc/liblrt_beams.so`` -- the beam rays: the sweep rays with per-beam elevation and azimuth offsets, and their pose, twist and table gradients
   (``csrc/lrt_beams.hip``, C ABI ``include/lrt_beams.h``): a fourteenth product library on the same pattern.  Loaded by ``lidar_rt_amd.beams``.
 
+* ``csrc/liblrt_reg.so`` -- the scan registration: projective point-to-plane ICP between two range images (``csrc/lrt_reg.hip``, C ABI
+  ``include/lrt_reg.h``): a fifteenth product library on the same pattern.  Loaded by ``lidar_rt_amd.registration``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -148,6 +151,11 @@ BEAMS_STAMP = os.path.join(CSRC, "liblrt_beams.srchash")
 BEAMS_SOURCES = ["lrt_beams.hip"]
 BEAMS_HEADERS = ["lrt_beams_math.h", "lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_beams.h"),
                  os.path.join("..", "..", "include", "lrt_sweep.h")]
+# the registration library: once more (it reads the rule headers of the projection and the sweep rays; their hashes do not read back)
+REG_LIB = os.path.join(CSRC, "liblrt_reg.so")
+REG_STAMP = os.path.join(CSRC, "liblrt_reg.srchash")
+REG_SOURCES = ["lrt_reg.hip"]
+REG_HEADERS = ["lrt_reg_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_reg.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -696,6 +704,46 @@ def build_beams(force: bool = False, verbose: bool = False) -> str:
     return BEAMS_LIB
 
 
+def reg_source_hash() -> str:
+    """source_hash() of the registration library: over ITS sources, headers (the two rule headers it reads included) and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(REG_SOURCES + REG_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def reg_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(REG_LIB):
+        return True
+    try:
+        return open(REG_STAMP).read().strip() != reg_source_hash()
+    except OSError:
+        return True
+
+
+def build_reg(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_reg.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other fourteen libraries."""
+    if force or reg_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", REG_LIB] \
+            + [os.path.join(CSRC, s) for s in REG_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(REG_STAMP, "w") as f:
+            f.write(reg_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(REG_LIB)} is up to date (sources {reg_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(REG_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return REG_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -804,6 +852,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_unproject(force, verbose)
     build_actorsweep(force, verbose)
     build_beams(force, verbose)
+    build_reg(force, verbose)
     return lib
 
 

@@ -1,7 +1,7 @@
 """Point clouds into a sequence directory: the converter that ``lidar_rt_amd/sequence.py`` promises, for any source of LiDAR scans.
 
     ingest_point_clouds(out_dir, clouds, H, W, inclination, data_type="KITTI", sensor2ego=None, max_depth=80.0, test_frames=(),
-                        boxes=None, init=None, device=None, batch=16, twists=None, compensated=False)
+                        boxes=None, init=None, device=None, batch=16, twists=None, compensated=False, odometry=None)
 
 ``clouds`` yields ``(frame_id, points (N, 4) [x, y, z, intensity] in the SENSOR frame, sensor2world (4, 4))``.  ``batch`` frames go through
 ``range_image.project_points`` per call (``device="cuda"``: the HIP operator; ``"cpu"``: its float64 twin; ``None``: the HIP device when there
@@ -15,12 +15,22 @@ instant.  ``compensated=True`` projects such frames with ``sweep_project.project
 the column that fired at it, with the range from that column's origin -- and stores the column times ``tau`` with each frame; ``ingest.json``
 then records ``compensated``, ``sweep_ref``, ``sweep_direction`` and seven counts (``unseen``: points in the gaps between the columns' bins).
 
+``odometry`` (a dict, possibly empty) is for scans that come WITHOUT poses: the ``sensor2world`` of ``clouds`` is ignored (it may be ``None``), the
+frames are projected first -- the projection never needed the pose -- and ``registration.odometry`` aligns every frame to the one before it
+(``registration.frame_geometry`` of the two range images, projective point-to-plane ICP).  Its keys: ``first_pose`` (4, 4) for the lowest id (the
+identity otherwise), ``sweep_fraction`` to also derive and store the twists from the poses found, and the keyword arguments of
+``registration.odometry`` (``schedule``, ``huber``, ``lam``, ``min_pairs``, ``tol_t``, ``tol_r``).  ``ingest.json`` gains ``"odometry"``: the
+schedule, every pair's status and final number of partners, and the pairs that kept the constant-velocity guess.  It does not go with
+``compensated``, which needs the twists before the projection.
+
     python -m lidar_rt_amd.ingest --points DIR --poses FILE --out DIR --height 66 --width 1030 --inclination -0.4346 0.0349
+    python -m lidar_rt_amd.ingest --points DIR --odometry --out DIR --height 66 --width 1030 --inclination -0.4346 0.0349
 
 ``--points DIR`` holds ``<id>.npy`` ``(N, 4)`` or KITTI-style ``<id>.bin`` (float32 quadruples), ids being integers.  ``--poses FILE`` is a ``.npy``
 ``(F, 4, 4)`` in the order of the sorted ids, or text rows of an id and 12 or 16 numbers (a 3 x 4 or 4 x 4 sensor-to-world matrix, row-major).
 A frame without a row takes the last earlier pose, as the reference's KITTI loader does (lib/dataloader/kitti_loader/__init__.py:199-242);
-``ingest.json`` records which frames did.  ``--missing-pose error`` refuses instead.
+``ingest.json`` records which frames did.  ``--missing-pose error`` refuses instead.  Exactly one of ``--poses`` and ``--odometry`` is given;
+``--first-pose FILE`` is the pose of the first frame under ``--odometry``.
 """
 from __future__ import annotations
 
@@ -41,14 +51,16 @@ INGEST_FORMAT = "lidar-rt-amd-ingest/1"
 def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclination, data_type: str = "KITTI", sensor2ego=None, max_depth: float = 80.0,
                         test_frames: Sequence[int] = (), boxes: Optional[dict] = None, init: Optional[dict] = None, device=None, batch: int = 16,
                         wrap: bool = True, notes: Optional[dict] = None, twists: Optional[dict] = None, compensated: bool = False, tau=None,
-                        sweep_ref: float = 0.5, sweep_direction: str = "cw") -> dict:
+                        sweep_ref: float = 0.5, sweep_direction: str = "cw", odometry: Optional[dict] = None) -> dict:
     """See the module text.  ``wrap``: ``range_image.project_points``'s; ``notes``: further entries for ``ingest.json``; ``twists``: {id: (6,)} the
     sensor's motion over each frame's sweep (``sweep.twists_from_poses``), stored with the frame for ``load_sequence(..., sweep="stored")`` -- without
     ``compensated`` the projection itself is not changed by it.  ``compensated``: the clouds are motion compensated (``twists`` is required): they
     are projected under the sweep model with the column times ``tau`` ((W,), else ``sweep.column_times(W, sweep_ref, sweep_direction)``), which are
-    stored with every frame.  Returns what ``ingest.json`` holds."""
+    stored with every frame.  ``odometry``: see the module text.  Returns what ``ingest.json`` holds."""
     if batch < 1:
         raise ValueError(f"ingest_point_clouds: batch {batch}")
+    if odometry is not None and (compensated or twists is not None):
+        raise ValueError("ingest_point_clouds: odometry finds the poses after the projection; compensated clouds and given twists need them before it")
     names = range_image.COUNT_NAMES
     if compensated:
         from . import sweep, sweep_project
@@ -97,7 +109,8 @@ def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclinat
                 raise ValueError(f"ingest_point_clouds: frame {fid}: points must be (N, 4) or (N, 3), they are {pts.shape}")
             if pts.shape[1] == 3:
                 pts = np.concatenate([pts, np.zeros((pts.shape[0], 1), pts.dtype)], 1)
-            group.append((fid, pts.astype(np.float32, copy=False), np.asarray(s2w.detach().cpu() if torch.is_tensor(s2w) else s2w, np.float64).reshape(4, 4)))
+            s2w = None if odometry is not None else np.asarray(s2w.detach().cpu() if torch.is_tensor(s2w) else s2w, np.float64).reshape(4, 4)
+            group.append((fid, pts.astype(np.float32, copy=False), s2w))
             if len(group) == batch:
                 yield from flush(group)
                 group = []
@@ -105,6 +118,8 @@ def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclinat
             yield from flush(group)
 
     done = list(frames())                                                    # every image first: the extent is known after the last one
+    if odometry is not None:
+        notes = {**(notes or {}), "odometry": _odometry(done, dict(odometry), H, W, inc, data_type, sensor2ego, dev)}
     meta = sequence.write_sequence(out_dir, done, data_type=data_type, extent=extent[0] if extent[0] > 0.0 else 1.0, sensor2ego=sensor2ego, boxes=boxes, init=init,
                                    test_frames=test_frames)
     total = {n: int(sum(f[n] for f in per_frame)) for n in names}
@@ -115,6 +130,37 @@ def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclinat
     with open(os.path.join(out_dir, "ingest.json"), "w") as f:
         json.dump(report, f, indent=1)
     return report
+
+
+class _Geometries:
+    """{id: registration.frame_geometry of the frame} made on access, the last two kept: odometry reads consecutive pairs in id order."""
+
+    def __init__(self, done, make):
+        self.by_id, self.make, self.kept = {int(fr["id"]): fr for fr in done}, make, {}
+
+    def __iter__(self):
+        return iter(self.by_id)
+
+    def __getitem__(self, i):
+        if i not in self.kept:
+            self.kept = {k: v for k, v in list(self.kept.items())[-1:]}
+            self.kept[i] = self.make(self.by_id[i])
+        return self.kept[i]
+
+
+def _odometry(done, opts, H, W, inc, data_type, sensor2ego, dev) -> dict:
+    """Poses (and, with ``sweep_fraction``, twists) for the projected frames ``done``, in place; returns the report's entry."""
+    from . import registration, sweep
+    fraction = opts.pop("sweep_fraction", None)
+    make = lambda fr: registration.frame_geometry(torch.from_numpy(np.ascontiguousarray(fr["depth"], np.float32)).to(dev),
+                                                  torch.from_numpy(np.ascontiguousarray(fr["mask"])).to(dev), inc, int(H), int(W), data_type, sensor2ego)
+    poses, rep = registration.odometry(_Geometries(done, make), inclination=inc, data_type=data_type, sensor2ego=sensor2ego, **opts)
+    twists = sweep.twists_from_poses(poses, fraction) if fraction is not None else None
+    for fr in done:
+        fr["sensor2world"] = poses[int(fr["id"])]
+        if twists is not None:
+            fr["twist"] = twists[int(fr["id"])]
+    return {"schedule": rep["schedule"], "pairs": rep["pairs"], "failed": rep["failed"], "first_pose": poses[min(poses)].tolist()}
 
 
 # ---- the command line ------------------------------------------------------------------------------------------------------------------------------------
@@ -178,7 +224,10 @@ def matrix_file(path: str) -> np.ndarray:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m lidar_rt_amd.ingest", description="Project point clouds into range images and write a sequence directory.")
     ap.add_argument("--points", required=True, help="directory of <id>.npy (N, 4) or KITTI-style <id>.bin float32 quadruples, points in the sensor frame")
-    ap.add_argument("--poses", required=True, help=".npy (F, 4, 4) in the order of the sorted ids, or text rows: id and 12 or 16 numbers (sensor to world)")
+    ap.add_argument("--poses", help=".npy (F, 4, 4) in the order of the sorted ids, or text rows: id and 12 or 16 numbers (sensor to world); this or --odometry")
+    ap.add_argument("--odometry", action="store_true", help="the scans come without poses: align every frame to the one before it (lidar_rt_amd.registration) "
+                    "and write the trajectory found; this or --poses")
+    ap.add_argument("--first-pose", help="--odometry: the pose of the first frame, a 4 x 4 (or 3 x 4) matrix, .npy or text (the identity otherwise)")
     ap.add_argument("--out", required=True, help="the sequence directory to write")
     ap.add_argument("--sensor2ego", help="a 4 x 4 (or 3 x 4) matrix, .npy or text: the yaw of Waymo data")
     ap.add_argument("--height", type=int, required=True)
@@ -201,12 +250,25 @@ def main(argv=None) -> int:
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None)
     ap.add_argument("--batch", type=int, default=16)
     a = ap.parse_args(argv)
+    if bool(a.poses) == bool(a.odometry):
+        print("ingest: give exactly one of --poses FILE and --odometry" + (" (both were given)" if a.poses else " (neither was given)"), file=sys.stderr)
+        return 2
+    if a.odometry and a.compensated:
+        print("ingest: --odometry does not go with --compensated: compensated clouds are projected under their twists, which would need a second "
+              "projection pass after the poses are found", file=sys.stderr)
+        return 2
+    if a.first_pose and not a.odometry:
+        print("ingest: --first-pose goes with --odometry", file=sys.stderr)
+        return 2
     if a.compensated and not a.sweep:
         print("ingest: --compensated needs --sweep (the twists the clouds were compensated with)", file=sys.stderr)
         return 2
     files = list_points(a.points)
     ids = [i for i, _ in files]
-    poses = read_poses(a.poses, ids)
+    if a.odometry and a.sweep and len(ids) < 2:
+        print("ingest: --sweep: twists from poses need at least two frames", file=sys.stderr)
+        return 2
+    poses = {i: None for i in ids} if a.odometry else read_poses(a.poses, ids)
     inc = list(a.inclination) if a.inclination else (np.load(a.beams) if a.beams.endswith(".npy") else np.loadtxt(a.beams)).reshape(-1).tolist()
     borrowed, use, last = {}, {}, None
     for i in ids:
@@ -219,7 +281,7 @@ def main(argv=None) -> int:
             borrowed[str(i)] = last
         use[i] = poses[last]
     twists = None
-    if a.sweep:
+    if a.sweep and not a.odometry:
         from . import sweep
         try:
             twists = sweep.twists_from_poses(use, a.sweep_fraction)
@@ -230,11 +292,14 @@ def main(argv=None) -> int:
     rep = ingest_point_clouds(a.out, clouds, a.height, a.width, inc, data_type=a.data_type, sensor2ego=matrix_file(a.sensor2ego) if a.sensor2ego else None,
                               max_depth=a.max_depth, test_frames=a.test_frames, device=a.device, batch=a.batch, wrap=not a.no_wrap,
                               notes={"pose_taken_from": borrowed, **({"sweep_fraction": float(a.sweep_fraction)} if a.sweep else {})}, twists=twists,
+                              **({"odometry": {**({"first_pose": matrix_file(a.first_pose)} if a.first_pose else {}),
+                                               **({"sweep_fraction": a.sweep_fraction} if a.sweep else {})}} if a.odometry else {}),
                               **(dict(compensated=True, sweep_ref=a.sweep_ref, sweep_direction=a.sweep_direction) if a.compensated else {}))
     t = rep["total"]
     unseen = f"{t['unseen']} unseen, " if a.compensated else ""
     print(f"ingest: {len(ids)} frames, {t['points']} points -> {t['pixels']} pixels ({t['hidden']} hidden, {t['out_of_view']} out of view, {unseen}"
-          f"{t['out_of_range']} out of range, {t['invalid']} invalid); {len(borrowed)} frames took an earlier pose; wrote {a.out}")
+          f"{t['out_of_range']} out of range, {t['invalid']} invalid); " + (f"{len(rep['odometry']['failed'])} of {len(rep['odometry']['pairs'])} pairs kept the constant-velocity guess"
+                                                                           if a.odometry else f"{len(borrowed)} frames took an earlier pose") + f"; wrote {a.out}")
     return 0
 
 
