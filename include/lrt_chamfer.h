@@ -23,9 +23,17 @@
  *              and symmetrically for (g2, idx2).  Like the reference binding the gradient buffers are ACCUMULATED
  *              into (dist_chamfer_3D.py:67-73 allocates them as zeros).
  *
+ * Non-finite inputs (a deliberate deviation from the reference, recorded in tests/test_chamfer_gpu.py):
+ *   A candidate whose distance to the query is NaN is never chosen and never hides another candidate.
+ *   If no candidate has a finite distance, the result is candidate 0's distance and index 0.
+ *   A NaN query therefore returns (NaN, 0).
+ *   The reference scans candidates in tiles of 512 and seeds every tile with its first candidate (chamfer3D.cu:35, :125): there a
+ *   NaN distance at the first candidate of a tile hides that whole tile, and one at candidate 0 becomes the result.  On clouds
+ *   with +-inf coordinates and no NaN distance the two agree.
+ *
  * Conventions: as in lrt.h -- device pointers to contiguous float32/int32, stream-ordered, 0 or a negative code
- * with lrt_last_error().  Inputs must be finite; N >= 1 and M >= 1 (the reference leaves its outputs
- * unwritten for an empty cloud; here that is LRT_ERR_ARG).
+ * with lrt_last_error().  N >= 1 and M >= 1 (the reference leaves its outputs unwritten for an empty cloud; here
+ * that is LRT_ERR_ARG).
  */
 #ifndef LRT_CHAMFER_H_INCLUDED
 #define LRT_CHAMFER_H_INCLUDED

@@ -5,7 +5,7 @@
 //   lib/utils/chamfer3D/chamfer3D.cu:154-173   NmDistanceGradKernel (6 atomics per point, x2 directions)
 //   lib/utils/chamfer3D/chamfer3D.cu:135-193   host launch code
 //
-// Design (DESIGN.md §9).  The reference scans all N*M pairs (1.7e10 for one 64x2048 LiDAR frame against its ground
+// Design (DESIGN.md §7.1).  The reference scans all N*M pairs (1.7e10 for one 64x2048 LiDAR frame against its ground
 // truth; ~3.5 ms of pure fp32 VALU time on this chip).  Here both clouds are Morton-sorted in ONE 32-bit radix sort
 // (key = cloud bit | 30-bit Morton code), an implicit 8-wide AABB tree is laid over each sorted cloud, and every
 // query point runs an exact nearest-neighbour descent (nearest child first, LDS stack).  The search is EXACT with
@@ -14,6 +14,9 @@
 // and fma are monotonic, so bound(box) <= d(q,p) for every p in the box holds in float32 and a box is skipped only
 // when bound > best.  Ties (d == best) keep the lower index, boxes with bound == best are still visited, hence
 // (dist, idx) are bit-identical to a brute-force scan in index order with `d < best`.
+// Non-finite inputs follow the contract of include/lrt_chamfer.h, not the reference's tiles: a candidate whose distance to the
+// query is NaN is never chosen and never hides another candidate; if no candidate has a finite distance, the result is
+// candidate 0's distance and index 0; a NaN query therefore returns (NaN, 0).
 // Mode 0 is that brute-force scan: candidates are wave-uniform (s_load -> SGPR broadcast, no LDS tile), each lane
 // owns 4 queries, candidate segments are merged with a 64-bit atomicMin on (dist bits << 32 | idx).
 #include <stdint.h>
@@ -85,6 +88,12 @@ __device__ __forceinline__ float ch_ord2f(unsigned u) { return __uint_as_float((
 
 // The pair distance of the reference (chamfer3D.cu:31-34 under nvcc's default fp contraction).
 __device__ __forceinline__ float ch_d2(float dx, float dy, float dz) { return __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx))); }
+
+// A query with a non-finite coordinate has no candidate at a finite distance (every pair distance is +inf or NaN), so its answer
+// is fixed (Chamfer: candidate 0; knn: no neighbour) and it must ask for NO box: its bounds are +inf.  Evaluated as written, the
+// bound of a NaN query would be 0 for every box (fmaxf drops the NaN gaps), the empty padding boxes included, whose children are
+// no boxes at all: the whole wave would walk into whatever memory follows and take it for candidates.
+__device__ __forceinline__ bool ch_finite3(float x, float y, float z) { return fabsf(x) < __uint_as_float(0x7f800000u) && fabsf(y) < __uint_as_float(0x7f800000u) && fabsf(z) < __uint_as_float(0x7f800000u); }
 
 __global__ void kc_init(unsigned* bounds)
 {
@@ -235,6 +244,7 @@ __global__ __launch_bounds__(CH_QBLOCK) void kc_query(ChParams p, int depth)
     const float4 q4 = p.pts[p.t[dir].pts_off + tid - (dir ? p.n[0] : 0)];      // queries in Morton order: neighbouring lanes walk alike
     const int qi = __float_as_int(q4.w);
     const float qx = q4.x, qy = q4.y, qz = q4.z;
+    const bool qfin = ch_finite3(qx, qy, qz);
     const float4* __restrict__ pts = p.pts + T.pts_off;
     const float* __restrict__ boxes = p.boxes;
     unsigned long long* stk = s_stack + threadIdx.x;
@@ -252,7 +262,7 @@ __global__ __launch_bounds__(CH_QBLOCK) void kc_query(ChParams p, int depth)
             const float gx = fmaxf(fmaxf(v[c] - qx, qx - v[24 + c]), 0.f);
             const float gy = fmaxf(fmaxf(v[8 + c] - qy, qy - v[32 + c]), 0.f);
             const float gz = fmaxf(fmaxf(v[16 + c] - qz, qz - v[40 + c]), 0.f);
-            lb[c] = ch_d2(gx, gy, gz);
+            lb[c] = qfin ? ch_d2(gx, gy, gz) : __uint_as_float(0x7f800000u);
         }
         int cmin = 0; float m = lb[0];
         for (int c = 1; c < 8; c++) if (lb[c] < m) { m = lb[c]; cmin = c; }
@@ -276,7 +286,7 @@ __global__ __launch_bounds__(CH_QBLOCK) void kc_query(ChParams p, int depth)
         }
         if (!have) break;
     }
-    if (besti == 0x7fffffff) {                              // non-finite input: the reference keeps candidate 0 (`k==0 ||`)
+    if (besti == 0x7fffffff) {                              // no candidate at a finite distance: candidate 0's distance, index 0 (the contract of lrt_chamfer.h)
         const float* c0 = p.xyz[1 - dir];
         best = ch_d2(c0[0] - qx, c0[1] - qy, c0[2] - qz); besti = 0;
     }
@@ -314,6 +324,7 @@ __global__ __launch_bounds__(64 * CH_PK_WAVES) void kc_query_pk(ChParams p, cons
     const bool valid = s0 + lane < Q.n;
     const float4 q4 = pts[Q.pts_off + (valid ? s0 + lane : s0)];          // padding lanes shadow the wave's first query
     const float qx = q4.x, qy = q4.y, qz = q4.z;
+    const bool qfin = ch_finite3(qx, qy, qz);
     const int myslot = valid ? s0 + lane : -1;
     const int nrow = (depth - 1) / 7 * 8;                    // one 8-row frame of per-lane bounds per level 2..K
     float* s_lb = s_pk + (size_t)wib * (nrow * 64 + depth);
@@ -334,7 +345,7 @@ __global__ __launch_bounds__(64 * CH_PK_WAVES) void kc_query_pk(ChParams p, cons
             const float gx = fmaxf(fmaxf(blk[c] - qx, qx - blk[24 + c]), 0.f);
             const float gy = fmaxf(fmaxf(blk[8 + c] - qy, qy - blk[32 + c]), 0.f);
             const float gz = fmaxf(fmaxf(blk[16 + c] - qz, qz - blk[40 + c]), 0.f);
-            lb[c] = ch_d2(gx, gy, gz);
+            lb[c] = qfin ? ch_d2(gx, gy, gz) : __uint_as_float(0x7f800000u);
         }
         if (k == 1) {
 #pragma unroll
@@ -346,7 +357,9 @@ __global__ __launch_bounds__(64 * CH_PK_WAVES) void kc_query_pk(ChParams p, cons
                     const float4 v = pp[e];                  // uniform address: scalar load
                     float d = ch_d2(v.x - qx, v.y - qy, v.z - qz);
                     if (KNN3) {
-                        if ((8 * j + c) * 8 + e == myslot) d = __uint_as_float(0x7f800000u);      // `if (i == idx) continue;`
+                        // `if (i == idx) continue;`, and a NaN distance changes nothing either (`knn[j] > dist` is false, :139):
+                        // +inf passes through the network below without replacing any of b0, b1, b2, a NaN would duplicate b0
+                        if ((8 * j + c) * 8 + e == myslot || d != d) d = __uint_as_float(0x7f800000u);
                         float t = fminf(b0, d); d = fmaxf(b0, d); b0 = t;                        // updateKBest<3>, simple_knn.cu:129-143
                         t = fminf(b1, d); d = fmaxf(b1, d); b1 = t;
                         b2 = fminf(b2, d);
@@ -399,7 +412,7 @@ __global__ __launch_bounds__(64 * CH_PK_WAVES) void kc_query_pk(ChParams p, cons
         return;
     }
     float best = __uint_as_float((unsigned)(bk >> 32)); int besti = (int)(unsigned)bk;
-    if (besti == 0x7fffffff) {                              // non-finite input: the reference keeps candidate 0 (`k==0 ||`)
+    if (besti == 0x7fffffff) {                              // no candidate at a finite distance: candidate 0's distance, index 0 (the contract of lrt_chamfer.h)
         const float* c0 = p.xyz[1 - dir];
         best = ch_d2(c0[0] - qx, c0[1] - qy, c0[2] - qz); besti = 0;
     }
@@ -451,7 +464,7 @@ __global__ void kc_brute_fin(int n, const unsigned long long* __restrict__ best,
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const unsigned long long b = best[i];
-    if (b == ~0ull) {                                       // non-finite input: the reference keeps candidate 0 (`k==0 ||`)
+    if (b == ~0ull) {                                       // no candidate at a finite distance: candidate 0's distance, index 0 (the contract of lrt_chamfer.h)
         dist[i] = ch_d2(c[0] - q[3 * (size_t)i], c[1] - q[3 * (size_t)i + 1], c[2] - q[3 * (size_t)i + 2]); idx[i] = 0;
         return;
     }

@@ -1,7 +1,8 @@
 """ctypes binding of the CPU Chamfer oracle (TEST INFRASTRUCTURE, not product code).
 
 Restates lib/utils/chamfer3D/chamfer3D.cu of the reference; see chamfer_oracle.c for citations and the
-parity-pinning status ("parity unpinned" against the CUDA binary; pinned against the float64 definition).
+parity-pinning status (pinned bit for bit against the reference's kernels as oracle/ref_build.py compiles them for gfx950;
+nvcc's choice of contraction in the CUDA binary stays unobserved).
 Only ``tests/``, ``__graft_entry__.smoke()`` and benchmark tools' ``cpu_baseline`` legs may import this module.
 """
 from __future__ import annotations
@@ -38,9 +39,10 @@ def chamfer_backward(xyz1, xyz2, graddist1, graddist2, idx1, idx2, prec: str = "
     return ga, gb
 
 
-def knn_mean_dist2(points):
-    """simple-knn `distCUDA2`: points (P,3) float32 -> (P,) mean squared distance to the 3 nearest other points."""
+def knn_mean_dist2(points, variant: int = 0):
+    """simple-knn `distCUDA2`: points (P,3) float32 -> (P,) mean squared distance to the 3 nearest other points.
+    ``variant`` selects the pair-distance expression as in chamfer_forward (0 .. 5 = d2_v0 .. d2_v5)."""
     a = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
     out = np.zeros(a.shape[0], np.float32)
-    lib().orc_knn_mean_dist2(C.c_int(a.shape[0]), _p(a), _p(out))
+    lib().orc_knn_mean_dist2(C.c_int(a.shape[0]), _p(a), _p(out), C.c_int(variant))
     return out

@@ -16,14 +16,27 @@
  *                         index order (direction 1 first) in float32, or in float64 (the *_f64 entry).
  *
  * Arithmetic: nvcc compiles :34 with fp contraction on; the chain is restated as
- * fmaf(dz,dz, fmaf(dy,dy, dx*dx)).  The other legal contraction, fmaf(dz,dz, fmaf(dx,dx, dy*dy)), differs by at
- * most 1 ulp of the result; orc_chamfer_forward's `variant` argument selects it (1) or no contraction (2) so that
- * tests can show the index set is insensitive to it away from exact near-ties.
+ * fmaf(dz,dz, fmaf(dy,dy, dx*dx)) (variant 0, an assumption).  The `variant` argument of orc_chamfer_forward and
+ * orc_knn_mean_dist2 selects every other way to contract (dx*dx + dy*dy) + dz*dz without re-associating it:
+ * 1 = fmaf(dz,dz, fmaf(dx,dx, dy*dy)), 2 = no contraction, 3 = fmaf(dx,dx, dy*dy) + dz*dz, 4 = fmaf(dy,dy, dx*dx) + dz*dz,
+ * 5 = fmaf(dz,dz, dx*dx + dy*dy).  They differ by an ulp or so of the result; the index set is insensitive to the choice away
+ * from exact near-ties.
  *
- * PARITY PINNING: the reference ships no test, fixture or Python fallback for this extension and its kernels are
- * CUDA-only, so they cannot be run here: "parity unpinned" against the CUDA binary.  The oracle is pinned instead
- * against the mathematical definition (float64 brute force via numpy in tests/test_chamfer_oracle.py) and against
- * the autograd contract of dist_chamfer_3D.py:31-82 (finite differences of the summed distances).
+ * Scan order: like the kernel, nn_dir scans the candidates in tiles of 512 (`batch`, :12), seeds EACH tile with its first
+ * candidate (`k==0 ||`, :35/:78/:120) and merges a tile into the result only when `k2==0 || result > best` (:125).  On finite
+ * inputs that is the plain scan with one seed at candidate 0.  On a NaN distance it is not: a NaN at the first candidate of a tile
+ * is kept as that tile's best (no `d < NaN` holds), so the tile contributes nothing (`result > NaN` is false), and a NaN from
+ * tile 0 stays the result for good.  A NaN elsewhere in a tile is skipped.  The oracle restates this as the reference computes it;
+ * the PRODUCT deliberately does not reproduce the lost tiles (include/lrt_chamfer.h).
+ *
+ * PARITY PINNING: the reference's two CUDA files need no OptiX; oracle/ref_build.py translates copies of them with hipify and
+ * compiles them for gfx950, and tests/test_reference_pin_gpu.py runs those kernels against this file, bit for bit: the build with
+ * -ffp-contract=off against variant 2, the build with hipcc's default contraction against variant 4 (measured: hipcc pairs dy*dy
+ * and dz*dz in a packed multiply and fuses only the first addition; it equals none of variants 0, 1, 2), on finite and non-finite
+ * inputs.  So the scan order, the seeding, the tie rule and the NaN behaviour are pinned to the reference's kernels as hipcc
+ * compiles them.  NOT pinned: which contraction nvcc chooses for :34 in the CUDA binary (variant 0 is the assumption; no machine
+ * this project runs on can observe it).  The oracle is also checked against the mathematical definition (float64 brute force in
+ * tests/test_chamfer_oracle.py) and the autograd contract of dist_chamfer_3D.py:31-82 (finite differences).
  */
 #include <math.h>
 #include <stdint.h>
@@ -32,19 +45,41 @@
 static inline float d2_v0(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 static inline float d2_v1(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dx, dx, dy * dy)); }
 static inline float d2_v2(float dx, float dy, float dz) { float a = dx * dx; float b = dy * dy; float c = dz * dz; float s = a + b; return s + c; }
+/* the remaining ways a compiler may contract (dx*dx + dy*dy) + dz*dz without re-associating it: only one of the two additions fused */
+static inline float d2_v3(float dx, float dy, float dz) { float c = dz * dz; return fmaf(dx, dx, dy * dy) + c; }
+static inline float d2_v4(float dx, float dy, float dz) { float c = dz * dz; return fmaf(dy, dy, dx * dx) + c; }
+static inline float d2_v5(float dx, float dy, float dz) { float a = dx * dx; float b = dy * dy; return fmaf(dz, dz, a + b); }
+static inline float d2(int variant, float dx, float dy, float dz)
+{
+    switch (variant) {
+    case 0: return d2_v0(dx, dy, dz);
+    case 1: return d2_v1(dx, dy, dz);
+    case 2: return d2_v2(dx, dy, dz);
+    case 3: return d2_v3(dx, dy, dz);
+    case 4: return d2_v4(dx, dy, dz);
+    default: return d2_v5(dx, dy, dz);
+    }
+}
 
+#define ORC_TILE 512   /* `batch`, chamfer3D.cu:12 */
 static void nn_dir(int n, const float* q, int m, const float* c, float* dist, int32_t* idx, int variant)
 {
 #pragma omp parallel for schedule(static)
     for (int j = 0; j < n; j++) {
         const float x1 = q[3 * (size_t)j], y1 = q[3 * (size_t)j + 1], z1 = q[3 * (size_t)j + 2];
-        float best = 0.f; int best_i = 0;
-        for (int k = 0; k < m; k++) {
-            const float x2 = c[3 * (size_t)k] - x1, y2 = c[3 * (size_t)k + 1] - y1, z2 = c[3 * (size_t)k + 2] - z1;
-            const float d = variant == 0 ? d2_v0(x2, y2, z2) : variant == 1 ? d2_v1(x2, y2, z2) : d2_v2(x2, y2, z2);
-            if (k == 0 || d < best) { best = d; best_i = k; }
+        float res = 0.f; int res_i = 0;
+        for (int k2 = 0; k2 < m; k2 += ORC_TILE) {
+            const int end_k = (m < k2 + ORC_TILE ? m : k2 + ORC_TILE) - k2;
+            float best = 0.f; int best_i = 0;
+            for (int k = 0; k < end_k; k++) {
+                const size_t g = (size_t)(k2 + k);
+                const float x2 = c[3 * g] - x1, y2 = c[3 * g + 1] - y1, z2 = c[3 * g + 2] - z1;
+                const float d = d2(variant, x2, y2, z2);
+                if (k == 0 || d < best) { best = d; best_i = k + k2; }       /* seeded per tile */
+            }
+            if (k2 == 0 || res > best) { res = best; res_i = best_i; }      /* strict merge: the first minimum wins across tiles */
         }
-        dist[j] = best; idx[j] = best_i;
+        dist[j] = res; idx[j] = res_i;
     }
 }
 
@@ -100,12 +135,16 @@ void orc_chamfer_backward_f64(int B, int N, const float* xyz1, int M, const floa
  *   The reference restricts the scan to 1024-point Morton boxes whose box distance is within the 3rd-neighbour bound
  *   found among the +-3 Morton neighbours (:157-177); that pruning never discards one of the true three nearest, so
  *   the full scan below returns the same three distances (a set: independent of scan order).
- *   Pair distance :131-133 under nvcc contraction = fmaf(dz,dz, fmaf(dy,dy, dx*dx)).
- * PARITY PINNING: "parity unpinned" against the CUDA binary (no upstream test / fixture); pinned against the float64
- * definition in tests/test_knn.py.
+ *   The Morton box the reference sorts by is reduced with `init = {0,0,0}` folded into both min and max (:192-201), so the
+ *   origin always lies inside it.  That changes only the order in which points are scanned, never the three distances.
+ *   A NaN distance is ignored (`knn[j] > dist` is false, :139), and so is +inf (FLT_MAX > inf is false).
+ *   Pair distance :135-136: `variant` as in orc_chamfer_forward (0 = fmaf(dz,dz, fmaf(dy,dy, dx*dx)), the assumed nvcc contraction).
+ * PARITY PINNING: as above -- the reference's own kernels, built by oracle/ref_build.py, are compared with this function bit for
+ * bit in tests/test_reference_pin_gpu.py (contraction off = variant 2, hipcc's default = variant 4), non-finite points included;
+ * nvcc's own choice of contraction stays unobserved.  Also pinned against the float64 definition in tests/test_knn.py.
  */
 #include <float.h>
-void orc_knn_mean_dist2(int P, const float* pts, float* out)
+void orc_knn_mean_dist2(int P, const float* pts, float* out, int variant)
 {
 #pragma omp parallel for schedule(static)
     for (int i = 0; i < P; i++) {
@@ -113,7 +152,8 @@ void orc_knn_mean_dist2(int P, const float* pts, float* out)
         float best[3] = {FLT_MAX, FLT_MAX, FLT_MAX};
         for (int k = 0; k < P; k++) {
             if (k == i) continue;
-            float dist = d2_v0(pts[3 * (size_t)k] - x, pts[3 * (size_t)k + 1] - y, pts[3 * (size_t)k + 2] - z);
+            const float dx = pts[3 * (size_t)k] - x, dy = pts[3 * (size_t)k + 1] - y, dz = pts[3 * (size_t)k + 2] - z;
+            float dist = d2(variant, dx, dy, dz);
             for (int j = 0; j < 3; j++)
                 if (best[j] > dist) { float t = best[j]; best[j] = dist; dist = t; }
         }

@@ -1,5 +1,7 @@
 """GPU parity of the Chamfer operator (through the C ABI) against the CPU oracle: BIT-EXACT distances and indices,
 brute-force and tree modes, plus the autograd contract of dist_chamfer_3D.py:31-82."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -8,6 +10,8 @@ from lidar_rt_amd import scenes
 from lidar_rt_amd.chamfer3D import _C as chamfer_3D
 from lidar_rt_amd.chamfer3D import chamfer_3DDist
 from oracle import chamfer as och
+from oracle import ref_build
+from tests import chamfer_nonfinite_cases as nf
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -113,6 +117,69 @@ def test_full_frame_tree_equals_brute_force_and_invariants():
     # swapping the clouds swaps the outputs
     sw = run_hip(b, a, 1)
     assert_bit_exact((sw[1], sw[0], sw[3], sw[2]), t)
+
+
+def contract_reference(a, b):
+    """The operator's rule for non-finite inputs (include/lrt_chamfer.h), float32, the oracle's d2_v0, candidates in index order:
+    a candidate whose distance to the query is NaN is never chosen and never hides another candidate; if no candidate has a finite
+    distance, the result is candidate 0's distance and index 0; a NaN query therefore returns (NaN, 0)."""
+    out = []
+    for q, c in ((a, b), (b, a)):
+        ds, js = [], []
+        for bi in range(q.shape[0]):
+            D = nf.pair_d2(q[bi], c[bi], 0)
+            j = np.where(np.isfinite(D), D, np.inf).argmin(1)              # the first minimum among the finite distances
+            j[~np.isfinite(D).any(1)] = 0
+            ds.append(D[np.arange(len(j)), j]); js.append(j.astype(np.int32))
+        out.append((np.stack(ds), np.stack(js)))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def assert_same_nan_aware(got, want, what):
+    for g, w, name in zip(got, want, ("dist1", "dist2", "idx1", "idx2")):
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, name)
+        if g.dtype == np.float32:
+            assert np.array_equal(np.isnan(g), np.isnan(w)), f"{what} {name}: NaN at different places"
+            bad = (g.view(np.int32) != w.view(np.int32)) & ~np.isnan(w)
+        else:
+            bad = g != w
+        assert not bad.any(), f"{what} {name}: {bad.sum()} of {g.size} differ, first at {np.argwhere(bad)[0]}"
+
+
+@pytest.mark.parametrize("mode", CH_MODES)
+@pytest.mark.parametrize("N,M", [(300, 1100), (64, 65)])
+def test_non_finite_inputs_follow_the_contract(N, M, mode):
+    """No test fed kc_query, kc_query_pk or kc_brute_fin a non-finite value before: every mode, bit for bit against the rule."""
+    a, b = nf.finite_pair(N, M, 1)
+    assert_bit_exact(contract_reference(a, b), och.chamfer_forward(a, b))       # on finite inputs the rule is the oracle
+    for name, (a, b) in nf.nonfinite_cases(N, M).items():
+        assert_same_nan_aware(run_hip(a, b, mode), contract_reference(a, b), f"{name} mode {mode}")
+
+
+@pytest.mark.skipif(not os.path.exists(ref_build.MANIFEST), reason="oracle/_ref/manifest.json does not exist: the reference binaries were not built")
+def test_product_deviates_from_the_reference_only_where_the_contract_says():
+    """The reference seeds every tile of 512 candidates with its first one: a NaN there hides the tile (at candidate 0: is the
+    result).  The product ignores the NaN candidate.  On +-inf clouds without a NaN distance the two agree."""
+    from tests.test_reference_pin_gpu import ref_chamfer
+    cases = nf.nonfinite_cases(300, 1100)
+    for mode in CH_MODES:
+        a, b = cases["nan_candidate_0"]
+        got, ref = run_hip(a, b, mode), ref_chamfer(a, b, "off")
+        assert np.isnan(ref[0]).all() and (ref[2] == 0).all()                   # the reference: poisoned for good
+        assert np.isfinite(got[0]).all() and (got[2] > 0).all()                 # the product: candidate 0 is never chosen
+        a, b = cases["nan_candidate_512"]
+        got, ref = run_hip(a, b, mode), ref_chamfer(a, b, "off")
+        lost = (got[2] >= 512) & (got[2] < 1024)                                # queries whose nearest neighbour lies in the hidden tile
+        assert lost.any() and not ((ref[2] >= 512) & (ref[2] < 1024)).any() and (ref[0][lost] > got[0][lost]).all()
+        assert np.array_equal(got[2][~lost], ref[2][~lost])                     # every other query: the same neighbour
+        for name in nf.INF_ONLY:
+            a, b = cases[name]
+            got, ref = run_hip(a, b, mode), ref_chamfer(a, b, "off")
+            assert not np.isnan(got[0]).any() and not np.isnan(got[1]).any()
+            assert np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]), f"{name} mode {mode}"
+            # the product evaluates d2_v0, this build of the reference d2_v2: one rounding apart (the bound of
+            # test_contraction_variant_moves_distances_by_an_ulp_at_most); +inf equals +inf
+            np.testing.assert_allclose(got[0], ref[0], rtol=2.5e-7, atol=0); np.testing.assert_allclose(got[1], ref[1], rtol=2.5e-7, atol=0)
 
 
 def test_backward_matches_oracle_and_accumulates():

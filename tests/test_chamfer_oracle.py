@@ -51,7 +51,7 @@ def test_first_minimum_wins_on_exact_ties():
 def test_contraction_variant_moves_distances_by_an_ulp_at_most():
     a, b = clouds(1, 400, 500, 11)
     base = och.chamfer_forward(a, b, 0)
-    for v in (1, 2):
+    for v in (1, 2, 3, 4, 5):
         alt = och.chamfer_forward(a, b, v)
         np.testing.assert_allclose(alt[0], base[0], rtol=2.5e-7, atol=0)
         assert (alt[2] == base[2]).mean() > 0.995
@@ -78,3 +78,58 @@ def test_backward_is_the_gradient_of_the_weighted_distance_sum():
             a64, b64 = a.astype(np.float64), b.astype(np.float64)
             fd = (loss(p, b64) - loss(m, b64)) / (2 * h) if which == 0 else (loss(a64, p) - loss(a64, m)) / (2 * h)
             assert abs(fd - g[bi, pi, ax]) <= 1e-4 * max(1.0, abs(fd)), (which, bi, pi, ax, fd, g[bi, pi, ax])
+
+
+# ---- the tile-faithful scan (chamfer3D.cu:12-131): tiles of 512, each seeded with its first candidate, merged strictly ----
+from tests import chamfer_nonfinite_cases as nf
+
+
+def tile_scan(D):
+    """NumPy restatement of NmDistanceKernel's loop over a (N,M) matrix of float32 pair distances (NaN allowed)."""
+    N, M = D.shape
+    res = np.zeros(N, np.float32); res_i = np.zeros(N, np.int32)
+    for k2 in range(0, M, nf.TILE):
+        T = D[:, k2:k2 + nf.TILE]
+        best = T[:, 0].copy(); best_i = np.full(N, k2, np.int32)              # `k==0 ||`: the tile's first candidate seeds it
+        for k in range(1, T.shape[1]):
+            upd = T[:, k] < best
+            best = np.where(upd, T[:, k], best); best_i = np.where(upd, np.int32(k2 + k), best_i)
+        take = np.ones(N, bool) if k2 == 0 else res > best                    # `k2==0 || result > best`
+        res = np.where(take, best, res); res_i = np.where(take, best_i, res_i)
+    return res, res_i
+
+
+def same_bits(got, want):
+    return got.dtype == want.dtype and got.shape == want.shape and np.array_equal(got.view(np.int32), want.view(np.int32))
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5])
+@pytest.mark.parametrize("M", [511, 512, 513, 1027, 4097])
+def test_tiled_scan_equals_the_single_seed_scan_on_finite_inputs(M, variant):
+    """On finite inputs the per-tile seeding is invisible: the result is the first minimum of the whole row."""
+    a, b = nf.finite_pair(37, M, 40 + M)
+    b[0, M // 2:M // 2 + 40] = b[0, 3:43]                                      # exact ties across the scan, some across a tile border
+    b[0, M - 1] = b[0, 0]
+    d1, d2, i1, i2 = och.chamfer_forward(a, b, variant)
+    for d, i, D in ((d1[0], i1[0], nf.pair_d2(a[0], b[0], variant)), (d2[0], i2[0], nf.pair_d2(b[0], a[0], variant))):
+        j = D.argmin(1)                                                        # first occurrence = one seed at candidate 0, strict `<`
+        assert np.array_equal(i, j.astype(np.int32)) and same_bits(d, D[np.arange(len(j)), j])
+
+
+@pytest.mark.parametrize("variant", [0, 2])
+def test_tiled_scan_on_non_finite_inputs_is_the_reference_loop(variant):
+    """NaN at a tile's first candidate hides the tile, NaN at candidate 0 stays the result, NaN elsewhere is skipped."""
+    cases = nf.nonfinite_cases(300, 1100)
+    for name, (a, b) in cases.items():
+        d1, d2, i1, i2 = och.chamfer_forward(a, b, variant)
+        for d, i, q, c in ((d1[0], i1[0], a[0], b[0]), (d2[0], i2[0], b[0], a[0])):
+            wd, wi = tile_scan(nf.pair_d2(q, c, variant))
+            assert same_bits(d, wd) and np.array_equal(i, wi), name
+    d1, _, i1, _ = och.chamfer_forward(*cases["nan_candidate_0"])
+    assert np.isnan(d1).all() and (i1 == 0).all()                              # poisoned for good
+    d1, _, i1, _ = och.chamfer_forward(*cases["nan_candidate_512"])
+    assert np.isfinite(d1).all() and not ((i1 >= 512) & (i1 < 1024)).any() and (i1 >= 1024).any()      # tile 1 lost, tile 2 kept
+    d1, _, i1, _ = och.chamfer_forward(*cases["nan_mid_tile"])
+    assert np.isfinite(d1).all() and ((i1 >= 512) & (i1 < 1024)).any() and not np.isin(i1, (100, 700)).any()
+    d1, d2, i1, i2 = och.chamfer_forward(*cases["nan_query"])
+    assert np.isnan(d1[0, 5]) and i1[0, 5] == 0 and np.isfinite(np.delete(d1[0], 5)).all() and not (i2 == 5).any()

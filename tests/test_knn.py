@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from oracle import chamfer as och
+from tests.chamfer_nonfinite_cases import knn_nonfinite_cloud
 
 
 def cloud(P, seed, scale=10.0):
@@ -20,6 +21,25 @@ def definition64(p):
 def test_oracle_matches_float64_definition(P):
     p = cloud(P, P)
     np.testing.assert_allclose(och.knn_mean_dist2(p), definition64(p), rtol=3e-6)
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5])
+@pytest.mark.parametrize("P", [4, 5, 257, 1500])
+def test_oracle_variants_match_float64_definition(P, variant):
+    p = cloud(P, P)
+    np.testing.assert_allclose(och.knn_mean_dist2(p, variant), definition64(p), rtol=3e-6)
+    if variant == 0:
+        assert np.array_equal(och.knn_mean_dist2(p, 0), och.knn_mean_dist2(p))          # the default is variant 0
+
+
+def test_oracle_ignores_non_finite_points():
+    """`knn[j] > dist` (simple_knn.cu:139) is false for a NaN and for a +inf distance: such a point is nobody's neighbour and has none."""
+    p = knn_nonfinite_cloud(300)
+    got = och.knn_mean_dist2(p)
+    bad = np.array([100, 200])
+    keep = np.delete(np.arange(300), bad)
+    assert np.isinf(got[bad]).all()                              # three FLT_MAX: the float32 sum overflows
+    assert np.array_equal(got[keep], och.knn_mean_dist2(p[keep]))
 
 
 def test_oracle_small_and_duplicate_clouds():
@@ -59,6 +79,19 @@ def test_hip_bit_exact_lidar_init_cloud_and_duplicates():
     assert np.array_equal(got.view(np.int32), want.view(np.int32)), f"{(got != want).sum()} differ"
     # gaussian_model.py:167-168 use: clamp_min(dist2, 1e-7) -> log(sqrt()) must be finite
     assert np.isfinite(np.log(np.sqrt(np.maximum(got, 1e-7)))).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P", [3000, 70])
+def test_hip_bit_exact_with_a_nan_and_an_inf_point(P):
+    """Raw LiDAR clouds carry NaN returns: a NaN distance must be ignored exactly as `knn[j] > dist` ignores it, for the finite
+    points whose search visits the NaN point's leaf and for the non-finite points themselves."""
+    from simple_knn._C import distCUDA2
+    p = knn_nonfinite_cloud(P, 20 + P)
+    got = distCUDA2(torch.as_tensor(p, device="cuda:0")).cpu().numpy()
+    want = och.knn_mean_dist2(p)
+    assert np.array_equal(got.view(np.int32), want.view(np.int32)), f"{(got.view(np.int32) != want.view(np.int32)).sum()} of {P} differ"
+    assert np.isinf(got[[P // 3, 2 * P // 3]]).all() and np.isfinite(np.delete(got, [P // 3, 2 * P // 3])).all()
 
 
 @pytest.mark.gpu
