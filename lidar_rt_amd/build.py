@@ -51,6 +51,10 @@
 * ``csrc/liblrt_reg.so`` -- the scan registration: projective point-to-plane ICP between two range images (``csrc/lrt_reg.hip``, C ABI
   ``include/lrt_reg.h``): a fifteenth product library on the same pattern.  Loaded by ``lidar_rt_amd.registration``.
 
+* ``csrc/liblrt_segment.so`` -- the range-image segmentation: ground, connected segments, free-space evidence, segment tables and track
+  bounds (``csrc/lrt_segment.hip``, C ABI ``include/lrt_segment.h``): a sixteenth product library on the same pattern.  Loaded by
+  ``lidar_rt_amd.segmentation``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -156,6 +160,11 @@ REG_LIB = os.path.join(CSRC, "liblrt_reg.so")
 REG_STAMP = os.path.join(CSRC, "liblrt_reg.srchash")
 REG_SOURCES = ["lrt_reg.hip"]
 REG_HEADERS = ["lrt_reg_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_reg.h")]
+# the segmentation library: once more (it reads the same two rule headers, as they are)
+SEGMENT_LIB = os.path.join(CSRC, "liblrt_segment.so")
+SEGMENT_STAMP = os.path.join(CSRC, "liblrt_segment.srchash")
+SEGMENT_SOURCES = ["lrt_segment.hip"]
+SEGMENT_HEADERS = ["lrt_segment_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_segment.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -744,6 +753,46 @@ def build_reg(force: bool = False, verbose: bool = False) -> str:
     return REG_LIB
 
 
+def segment_source_hash() -> str:
+    """source_hash() of the segmentation library: over ITS sources, headers (the two rule headers it reads included) and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(SEGMENT_SOURCES + SEGMENT_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def segment_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(SEGMENT_LIB):
+        return True
+    try:
+        return open(SEGMENT_STAMP).read().strip() != segment_source_hash()
+    except OSError:
+        return True
+
+
+def build_segment(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_segment.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other fifteen libraries."""
+    if force or segment_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", SEGMENT_LIB] \
+            + [os.path.join(CSRC, s) for s in SEGMENT_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(SEGMENT_STAMP, "w") as f:
+            f.write(segment_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(SEGMENT_LIB)} is up to date (sources {segment_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(SEGMENT_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return SEGMENT_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -853,6 +902,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_actorsweep(force, verbose)
     build_beams(force, verbose)
     build_reg(force, verbose)
+    build_segment(force, verbose)
     return lib
 
 

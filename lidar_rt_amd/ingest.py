@@ -1,7 +1,7 @@
 """Point clouds into a sequence directory: the converter that ``lidar_rt_amd/sequence.py`` promises, for any source of LiDAR scans.
 
     ingest_point_clouds(out_dir, clouds, H, W, inclination, data_type="KITTI", sensor2ego=None, max_depth=80.0, test_frames=(),
-                        boxes=None, init=None, device=None, batch=16, twists=None, compensated=False, odometry=None)
+                        boxes=None, init=None, device=None, batch=16, twists=None, compensated=False, odometry=None, discover_actors=None)
 
 ``clouds`` yields ``(frame_id, points (N, 4) [x, y, z, intensity] in the SENSOR frame, sensor2world (4, 4))``.  ``batch`` frames go through
 ``range_image.project_points`` per call (``device="cuda"``: the HIP operator; ``"cpu"``: its float64 twin; ``None``: the HIP device when there
@@ -23,8 +23,13 @@ identity otherwise), ``sweep_fraction`` to also derive and store the twists from
 schedule, every pair's status and final number of partners, and the pairs that kept the constant-velocity guess.  It does not go with
 ``compensated``, which needs the twists before the projection.
 
+``discover_actors`` (a dict with ``sensor_height`` and, optionally, the keyword arguments of ``actors.discover``) runs ``lidar_rt_amd.actors.discover`` on
+the projected frames once their poses are known -- given, or found by ``odometry`` -- and writes the moving actors' tracking boxes as ``boxes.npz``
+and the report as ``actors.json``: what ``python -m lidar_rt_amd.actors`` adds to a finished sequence.  It does not go with ``boxes``.
+
     python -m lidar_rt_amd.ingest --points DIR --poses FILE --out DIR --height 66 --width 1030 --inclination -0.4346 0.0349
     python -m lidar_rt_amd.ingest --points DIR --odometry --out DIR --height 66 --width 1030 --inclination -0.4346 0.0349
+    python -m lidar_rt_amd.ingest --points DIR --odometry --discover-actors --sensor-height 1.8 --out DIR --height 66 --width 1030 --inclination ...
 
 ``--points DIR`` holds ``<id>.npy`` ``(N, 4)`` or KITTI-style ``<id>.bin`` (float32 quadruples), ids being integers.  ``--poses FILE`` is a ``.npy``
 ``(F, 4, 4)`` in the order of the sorted ids, or text rows of an id and 12 or 16 numbers (a 3 x 4 or 4 x 4 sensor-to-world matrix, row-major).
@@ -51,7 +56,8 @@ INGEST_FORMAT = "lidar-rt-amd-ingest/1"
 def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclination, data_type: str = "KITTI", sensor2ego=None, max_depth: float = 80.0,
                         test_frames: Sequence[int] = (), boxes: Optional[dict] = None, init: Optional[dict] = None, device=None, batch: int = 16,
                         wrap: bool = True, notes: Optional[dict] = None, twists: Optional[dict] = None, compensated: bool = False, tau=None,
-                        sweep_ref: float = 0.5, sweep_direction: str = "cw", odometry: Optional[dict] = None) -> dict:
+                        sweep_ref: float = 0.5, sweep_direction: str = "cw", odometry: Optional[dict] = None,
+                        discover_actors: Optional[dict] = None) -> dict:
     """See the module text.  ``wrap``: ``range_image.project_points``'s; ``notes``: further entries for ``ingest.json``; ``twists``: {id: (6,)} the
     sensor's motion over each frame's sweep (``sweep.twists_from_poses``), stored with the frame for ``load_sequence(..., sweep="stored")`` -- without
     ``compensated`` the projection itself is not changed by it.  ``compensated``: the clouds are motion compensated (``twists`` is required): they
@@ -61,6 +67,10 @@ def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclinat
         raise ValueError(f"ingest_point_clouds: batch {batch}")
     if odometry is not None and (compensated or twists is not None):
         raise ValueError("ingest_point_clouds: odometry finds the poses after the projection; compensated clouds and given twists need them before it")
+    if discover_actors is not None and boxes is not None:
+        raise ValueError("ingest_point_clouds: discover_actors finds the boxes; it does not go with given boxes")
+    if discover_actors is not None and "sensor_height" not in discover_actors:
+        raise ValueError("ingest_point_clouds: discover_actors needs sensor_height (the height of the sensor above the ground, metres)")
     names = range_image.COUNT_NAMES
     if compensated:
         from . import sweep, sweep_project
@@ -120,6 +130,15 @@ def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclinat
     done = list(frames())                                                    # every image first: the extent is known after the last one
     if odometry is not None:
         notes = {**(notes or {}), "odometry": _odometry(done, dict(odometry), H, W, inc, data_type, sensor2ego, dev)}
+    actors_report = None
+    if discover_actors is not None:
+        from . import actors
+        opts = dict(discover_actors)
+        found, actors_report = actors.discover_images({int(fr["id"]): (fr["depth"], fr["mask"]) for fr in done}, {int(fr["id"]): np.asarray(fr["sensor2world"], np.float32).astype(np.float64) for fr in done},      # the poses as the frames store them
+                                                     
+                                                      opts.pop("sensor_height"), inc, data_type, sensor2ego, dev, **opts)
+        boxes = found if actors_report["n_actors"] else None
+        notes = {**(notes or {}), "actors": {"n_actors": actors_report["n_actors"], "tracks": len(actors_report["tracks"])}}
     meta = sequence.write_sequence(out_dir, done, data_type=data_type, extent=extent[0] if extent[0] > 0.0 else 1.0, sensor2ego=sensor2ego, boxes=boxes, init=init,
                                    test_frames=test_frames)
     total = {n: int(sum(f[n] for f in per_frame)) for n in names}
@@ -129,6 +148,8 @@ def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclinat
               **({"compensated": True, "sweep_ref": float(sweep_ref), "sweep_direction": sweep_direction} if compensated else {}), **(notes or {})}
     with open(os.path.join(out_dir, "ingest.json"), "w") as f:
         json.dump(report, f, indent=1)
+    if actors_report is not None:
+        actors.write_report(out_dir, actors_report)
     return report
 
 
@@ -247,9 +268,15 @@ def main(argv=None) -> int:
                     "instant, as KITTI, nuScenes and Waymo publish them): project them under the sweep model (lidar_rt_amd.sweep_project)")
     ap.add_argument("--sweep-ref", type=float, default=0.5, help="--compensated: the part of the sweep at which a frame's pose holds (0 = its first column, 0.5 = its middle)")
     ap.add_argument("--sweep-direction", choices=("cw", "ccw"), default="cw", help="--compensated: cw = time rises with the column index (a clockwise-spinning sensor)")
+    ap.add_argument("--discover-actors", action="store_true", help="once the poses are known (--poses or --odometry), find the moving actors "
+                    "(lidar_rt_amd.actors) and write their tracking boxes as boxes.npz, the report as actors.json; needs --sensor-height")
+    ap.add_argument("--sensor-height", type=float, help="--discover-actors: the height of the sensor above the ground [m]")
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None)
     ap.add_argument("--batch", type=int, default=16)
     a = ap.parse_args(argv)
+    if a.discover_actors != (a.sensor_height is not None):
+        print("ingest: --discover-actors and --sensor-height Z go together", file=sys.stderr)
+        return 2
     if bool(a.poses) == bool(a.odometry):
         print("ingest: give exactly one of --poses FILE and --odometry" + (" (both were given)" if a.poses else " (neither was given)"), file=sys.stderr)
         return 2
@@ -294,12 +321,14 @@ def main(argv=None) -> int:
                               notes={"pose_taken_from": borrowed, **({"sweep_fraction": float(a.sweep_fraction)} if a.sweep else {})}, twists=twists,
                               **({"odometry": {**({"first_pose": matrix_file(a.first_pose)} if a.first_pose else {}),
                                                **({"sweep_fraction": a.sweep_fraction} if a.sweep else {})}} if a.odometry else {}),
-                              **(dict(compensated=True, sweep_ref=a.sweep_ref, sweep_direction=a.sweep_direction) if a.compensated else {}))
+                              **(dict(compensated=True, sweep_ref=a.sweep_ref, sweep_direction=a.sweep_direction) if a.compensated else {}),
+                              **({"discover_actors": {"sensor_height": a.sensor_height}} if a.discover_actors else {}))
     t = rep["total"]
     unseen = f"{t['unseen']} unseen, " if a.compensated else ""
     print(f"ingest: {len(ids)} frames, {t['points']} points -> {t['pixels']} pixels ({t['hidden']} hidden, {t['out_of_view']} out of view, {unseen}"
           f"{t['out_of_range']} out of range, {t['invalid']} invalid); " + (f"{len(rep['odometry']['failed'])} of {len(rep['odometry']['pairs'])} pairs kept the constant-velocity guess"
-                                                                           if a.odometry else f"{len(borrowed)} frames took an earlier pose") + f"; wrote {a.out}")
+                                                                           if a.odometry else f"{len(borrowed)} frames took an earlier pose")
+          + (f"; {rep['actors']['n_actors']} moving actors" if a.discover_actors else "") + f"; wrote {a.out}")
     return 0
 
 

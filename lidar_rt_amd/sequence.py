@@ -107,6 +107,32 @@ def write_sequence(root: str, frames: Iterable[dict], data_type: str = "KITTI", 
     return meta
 
 
+def write_boxes(root: str, boxes: dict, force: bool = False) -> dict:
+    """Add tracking boxes (``lidar_rt_amd.actors.discover``) to a sequence that ``write_sequence`` wrote: ``boxes.npz`` and the ``dynamic`` /
+    ``n_actors`` fields of ``meta.json``, exactly as ``write_sequence(boxes=...)`` writes them.  An existing ``boxes.npz`` is refused without ``force``.
+    Returns the meta dictionary it wrote."""
+    mp, bp = os.path.join(root, "meta.json"), os.path.join(root, "boxes.npz")
+    with open(mp) as f:
+        meta = json.load(f)
+    if meta.get("format") != FORMAT:
+        raise ValueError(f"{root}: not a {FORMAT} directory (format = {meta.get('format')!r})")
+    if os.path.exists(bp) and not force:
+        raise FileExistsError(f"{bp} exists (force=True overwrites it)")
+    npy = lambda a, dt=np.float32: np.ascontiguousarray((a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dt))
+    A = np.asarray(boxes["translation"]).shape[0]
+    F_ = len(boxes["frames"])
+    unknown = sorted(set(int(i) for i in boxes["frames"]) - set(int(i) for i in meta["frames"]))
+    if unknown:
+        raise ValueError(f"{root}: the boxes name frames the sequence does not have: {unknown}")
+    np.savez(bp, frames=np.asarray(boxes["frames"], np.int64), translation=npy(boxes["translation"]).reshape(A, F_, 3),
+             quaternion=npy(boxes["quaternion"]).reshape(A, F_, 4), valid=npy(boxes.get("valid", np.ones((A, F_), bool)), np.bool_).reshape(A, F_),
+             size=npy(boxes["size"]).reshape(A, 3), **({} if boxes.get("twist") is None else {"twist": npy(boxes["twist"]).reshape(A, F_, 6)}))
+    meta["dynamic"], meta["n_actors"] = True, int(A)
+    with open(mp, "w") as f:
+        json.dump(meta, f, indent=1)
+    return meta
+
+
 SWEEP_MODES = (None, "off", "stored", "poses")
 ACTOR_SWEEP_MODES = (None, "off", "stored", "boxes")
 
