@@ -1,5 +1,7 @@
 """Ray-drop refinement without a GPU: the module against the reference's recorded outputs (tests/golden/refine_unet.npz), the folded batch
-norms, refine_raydrop on CPU tensors, the training stage on a stub renderer, and the refiner argument of the evaluation loop."""
+norms, refine_raydrop on CPU tensors, the training stage on a stub renderer, the refiner argument of the evaluation loop, and the GPU tests' own footing: which kernel
+paths their cases reach (a restatement of the launcher), what their two gates reject (the float32 module with deliberate errors), and the twin of
+the workspace plan."""
 import os
 import re
 import subprocess
@@ -238,6 +240,161 @@ def test_render_frames_hands_each_render_to_the_refiner(monkeypatch):
     assert torch.equal(r3[1]["raydrop"], rr.refine_raydrop(rc.frame(H, W, seed=1)[0], None, net3))
 
 
+# ---- what the cases of the GPU tests reach ---------------------------------------------------------------------------------------------------------------------
+
+def conv_launches(c, H, W):
+    """Every k_rf_conv launch of one frame in stream order, (layer, taps, pixels, Cin, Cout): the loop over the pairs in lrt_refine_forward
+    (lrt_refine.hip, `for (int i = 0; i < RF_PAIRS; i++)`) with rf_pair_channels of lrt_refine_math.h -- in, out and level per pair in units of c,
+    the middle width the output's going down and the input's going up -- and the two 1 x 1 projections of the attention block before pair 4."""
+    n = [(H >> l) * (W >> l) for l in range(5)]
+    names = ("down1", "down2", "down3", "down4", "up1", "up2", "up3", "up4")
+    out = []
+    for i, (ci, co, lvl) in enumerate(zip((1, 2, 4, 8, 16, 8, 4, 2), (2, 4, 8, 8, 4, 2, 1, 1), (1, 2, 3, 4, 3, 2, 1, 0))):
+        if i == 4:
+            out += [("attn.qkv", 1, n[4], 8 * c, 24 * c), ("attn.proj", 1, n[4], 8 * c, 8 * c)]
+        cm = co if i < 4 else ci
+        out += [(names[i] + ".1", 9, n[lvl], ci * c, cm * c), (names[i] + ".2", 9, n[lvl], cm * c, co * c)]
+    return out
+
+
+def conv_variant(pixels, Cin, Cout):
+    """(NT, KS, m_tiles) as launch_conv of lrt_refine.hip chooses them: one 32 x 32 tile per wave gives `waves`; at most 2048 of them and Cin a
+    multiple of 8 x 4: K split over the four waves; an even number of column tiles and at least 4096 waves of two tiles: NT = 2; else the plain kernel."""
+    m_tiles, n_tiles = (pixels + 31) // 32, (Cout + 31) // 32
+    waves = m_tiles * n_tiles
+    if waves <= 2048 and Cin % 32 == 0:
+        return 1, 4, m_tiles
+    if n_tiles % 2 == 0 and waves // 2 >= 4096:
+        return 2, 1, m_tiles
+    return 1, 1, m_tiles
+
+
+def paths_of(case):
+    """{(path, (NT, KS))} that one case runs; the paths are those listed in tests/refine_cases.py.  Attention and the frame's size have no variant."""
+    C, c, H, W = case
+    reached = set()
+    for layer, taps, pixels, Cin, Cout in conv_launches(c, H, W):
+        NT, KS, m_tiles = conv_variant(pixels, Cin, Cout)
+        c_per = Cin // KS                                                    # k_rf_conv: `c_per = g.Cin / KS`, the channel range of one wave
+        if c_per > 32 and c_per % 32 != 0:                                   # `for (; c0 + 32 <= c_end; ...)` runs and leaves a rest to `for (; c0 < c_end; ...)`
+            reached.add(("1", (NT, KS)))
+        if Cout > 32 and Cout % 32 != 0:                                     # `col_ok[t] = n0 + 32 t + r < g.Cout` is false on some lanes of a tile with n0 + 32 t >= 32
+            reached.add(("2", (NT, KS)))
+        if NT == 2 and pixels % 32 != 0 and m_tiles % 4 != 0:                # `if (q < n_pix)` in the store, `if (tile * 32 >= n_pix) return` for whole waves
+            reached.add(("3", (NT, KS)))
+        if (H >> 4, W >> 4) == (1, 1) and pixels < 32 and (NT, KS) == (1, 1):
+            reached.add(("5 a level under 32 pixels", (NT, KS)))
+    T = (H >> 4) * (W >> 4)
+    if T > 64 and T % 64 != 0:                                               # k_rf_attn: `for (int s = lane; s < T; s += 64)` ends on different rounds for different lanes
+        reached.add(("4 ragged", None))
+    if T == 1:
+        reached.add(("4 one token", None))
+    if (H >> 4, W >> 4) == (1, 1):                                           # rf_up_scale(1) = 0: up1 samples a single pixel
+        reached.add(("5 a 1 x 1 bottom", None))
+    return reached
+
+
+def test_the_new_cases_reach_what_the_first_ones_never_run(refine_lib):
+    old = set().union(*(paths_of(case) for case in rc.CASES))
+    new = set().union(*(paths_of(case) for case in rc.NEW_CASES))
+    # the first cases run all three kernel variants and none of the paths; NT = 2 only at 64 x 2048, where pixels and tiles are exact
+    variants = {conv_variant(p, ci, co)[:2] for case in rc.CASES for _, _, p, ci, co in conv_launches(case[1], case[2], case[3])}
+    assert variants == {(1, 4), (2, 1), (1, 1)}
+    assert old == set(), old
+    # paths 1 and 2 can occur in every variant (at NT = 2 only from 131072 pixels on at a width other than 32: the last case), path 3 at NT = 2,
+    # a level under 32 pixels only in the plain kernel: the K-split kernel has one tile per workgroup whatever the level's size
+    want = {("1", (1, 4)), ("1", (1, 1)), ("1", (2, 1)), ("2", (1, 4)), ("2", (1, 1)), ("2", (2, 1)), ("3", (2, 1)), ("4 ragged", None), ("4 one token", None),
+            ("5 a level under 32 pixels", (1, 1)), ("5 a 1 x 1 bottom", None)}
+    assert new == want, new ^ want
+    assert {("3", (2, 1))} == paths_of((9, 32, 65, 2017)) - {("4 ragged", None)}
+    assert {case[1] for case in rc.CASES + rc.NEW_CASES} == set(rc.WIDTHS) and {case[0] for case in rc.NEW_CASES} == {3, 9}
+    lib = rr.load()
+    assert [c for c in range(0, 81, 8) if lib.lrt_refine_work_bytes(64, 256, 9, c) > 0] == list(rc.WIDTHS)
+    # the attention sizes that the issue names, and the long chain of the widest network
+    tokens = {case: (case[2] >> 4) * (case[3] >> 4) for case in rc.NEW_CASES}
+    assert tokens[(9, 24, 80, 210)] == 65 and tokens[(9, 8, 17, 1100)] == 68 and tokens[(9, 32, 65, 2017)] == 504 and tokens[(9, 8, 16, 16)] == 1
+    assert max(taps * Cin for _, taps, _, Cin, _ in conv_launches(64, 33, 75)) == 9216
+    assert len(set(rc.CASES + rc.NEW_CASES)) == len(rc.CASES) + len(rc.NEW_CASES) == 26
+
+
+@pytest.mark.parametrize("C,c,H,W", rc.NEW_CASES, ids=lambda v: str(v))
+def test_the_new_cases_keep_the_conditions_of_the_mask_test(C, c, H, W):
+    z64, z32, e_f32 = rc.references(C, c, H, W)
+    assert bool(torch.isfinite(z64).all()) and bool(torch.isfinite(z32).all()) and 0.0 < e_f32 < 1e-5
+    near = (z64 - rc.LOGIT_04).abs() <= rc.K * e_f32
+    differ32 = (torch.sigmoid(z32) < 0.4) != (z64 < rc.LOGIT_04)
+    drops = float((z64 < rc.LOGIT_04).double().mean())
+    print(f"refine {C} inputs, channels {c}, {H}x{W}: e_f32 {e_f32:.3e}, {int(near.sum())} near, float32 module {int(differ32.sum())} differ, "
+          f"allowance {rc.MASK_CAP * H * W:.1f} pixels, {drops:.2f} of the mask dropped")
+    assert int(near.sum()) <= rc.MASK_CAP * H * W and int(differ32.sum()) <= rc.MASK_CAP * H * W
+    assert 0.0 < drops < 1.0                                                 # hits and drops alike: the mask comparison is not vacuous
+
+
+# ---- negative controls: what the two gates of the GPU tests reject ----------------------------------------------------------------------------------------------
+
+def _stand_in(case, damage):
+    """(logit error, e_f32 of the logits, layer ratios) of the float32 CPU module with one deliberate error, gated exactly as the operator is."""
+    import copy
+    C, c, H, W = case
+    net = copy.deepcopy(rc.network(C, c))
+    with torch.no_grad():
+        damage(net)
+    z, got = rc.collect(net, rc.case_input(C, H, W))
+    z64, _, e_f32 = rc.references(C, c, H, W)
+    b64, _, layer_e_f32 = rc.layer_references(C, c, H, W)
+    return float((z.double() - z64).abs().max()), e_f32, rc.layer_ratios(got, b64, layer_e_f32)
+
+
+def _drop_the_last_key(net):
+    def attend(x):                                                           # RaydropUNet._attend with every softmax over the keys 0 .. T - 2
+        a = net.attn
+        B, Cc, H, W = x.shape
+        d = Cc // rr.HEADS
+        qkv = a.proj_qkv(a.norm(x)).reshape(B, 3, rr.HEADS, d, H * W)
+        q, k, v = qkv[:, 0], qkv[:, 1][..., :-1], qkv[:, 2][..., :-1]
+        w = (q.transpose(-1, -2) @ k) * (int(d) ** -0.5)
+        h = (torch.softmax(w, dim=-1) @ v.transpose(-1, -2)).contiguous()
+        return x + a.proj(h.reshape(B, H, W, Cc).permute(0, 3, 1, 2))
+    net._attend = attend
+
+
+def test_an_undamaged_stand_in_passes_both_gates():
+    e_op, e_f32, ratios = _stand_in((9, 24, 33, 75), lambda net: None)
+    assert e_op <= e_f32 and rc.rejected_layers(ratios, 1.0) == []
+
+
+def test_a_softmax_short_of_one_key_passes_the_logit_gate_and_fails_the_layer_gate():
+    # T = 65: the key that a loop over whole rounds of 64 lanes would lose.  The logits move by less than the float32 module's own error, which
+    # is why the layers are gated: this assertion records it, the next ones are the gate
+    e_op, e_f32, ratios = _stand_in((9, 24, 80, 210), _drop_the_last_key)
+    print(f"last key dropped: logits {e_op:.3e} against a gate of {rc.K * e_f32:.3e}; HB {ratios['HB'][2]:.1f}, X4A {ratios['X4A'][2]:.1f} times their allowances")
+    assert e_op <= rc.K * e_f32
+    bad = rc.rejected_layers(ratios, rc.K_CAP)
+    assert "HB" in bad and "X4A" in bad and not set(bad) & {"X0", "M1", "X1", "M2", "X2", "M3", "X3", "M4", "X4", "QKV"}
+
+
+def test_lost_remainder_channels_fail_both_gates():
+    # channels = 24: the first convolution of down2 sums 48 input channels per tap, 32 in a four-group step and 16 in two single steps
+    def damage(net):
+        net.down2.conv.double_conv[3].weight[:, 32:48] = 0.0
+    e_op, e_f32, ratios = _stand_in((9, 24, 33, 75), damage)
+    print(f"remainder channels lost: logits {e_op / (rc.K * e_f32):.0f} gates, M2 {ratios['M2'][2]:.0f} allowances")
+    assert e_op > rc.K * e_f32 and e_op > rc.K_CAP * e_f32
+    bad = rc.rejected_layers(ratios, rc.K_CAP)
+    assert bad[0] == "M2" and "X0" not in bad and "M1" not in bad and "X1" not in bad
+
+
+def test_lost_output_channels_of_a_partial_column_tile_fail_both_gates():
+    # channels = 24: the first convolution of down1 writes 48 output channels, the second column tile holds 16
+    def damage(net):
+        net.down1.conv.double_conv[3].weight[32:] = 0.0
+    e_op, e_f32, ratios = _stand_in((9, 24, 33, 75), damage)
+    print(f"output channels lost: logits {e_op / (rc.K * e_f32):.0f} gates, M1 {ratios['M1'][2]:.0f} allowances")
+    assert e_op > rc.K * e_f32 and e_op > rc.K_CAP * e_f32
+    bad = rc.rejected_layers(ratios, rc.K_CAP)
+    assert bad[0] == "M1" and "X0" not in bad
+
+
 # ---- the library ---------------------------------------------------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
@@ -288,6 +445,19 @@ def test_the_library_builds_and_exports_what_its_header_declares(refine_lib):
             rr.work_bytes(H, W, 9, 32)
     with pytest.raises(rr.RefineError, match="multiple of 8"):
         rr.work_bytes(64, 256, 9, 12)
+
+
+def test_the_plan_twin_has_the_size_of_the_operators_workspace(refine_lib):
+    lib = rr.load()
+    for C, c, H, W in rc.CASES + rc.NEW_CASES:
+        offsets, total = rc.plan(c, H, W)
+        assert list(offsets) == list(rc.BUFFERS) and len(offsets) == 20
+        assert 4 * total == lib.lrt_refine_work_bytes(H, W, C, c) == rr.work_bytes(H, W, C, c), (C, c, H, W)
+        end = 0
+        for b, (off, level, ch) in offsets.items():                          # nothing is aliased: each buffer starts at or behind the end of the one before
+            assert off % 64 == 0 and off >= end and 0 <= level <= 4 and ch % c == 0
+            end = off + (H >> level) * (W >> level) * ch
+        assert end <= total
 
 
 def test_the_kernels_pass_the_resource_gate(refine_lib):
