@@ -55,6 +55,9 @@
   bounds (``csrc/lrt_segment.hip``, C ABI ``include/lrt_segment.h``): a sixteenth product library on the same pattern.  Loaded by
   ``lidar_rt_amd.segmentation``.
 
+* ``csrc/liblrt_place.so`` -- the place matcher: one ring-by-sector descriptor per scan and every scan against every earlier scan at every yaw
+  (``csrc/lrt_place.hip``, C ABI ``include/lrt_place.h``): a seventeenth product library on the same pattern.  Loaded by ``lidar_rt_amd.place``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -165,6 +168,11 @@ SEGMENT_LIB = os.path.join(CSRC, "liblrt_segment.so")
 SEGMENT_STAMP = os.path.join(CSRC, "liblrt_segment.srchash")
 SEGMENT_SOURCES = ["lrt_segment.hip"]
 SEGMENT_HEADERS = ["lrt_segment_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_segment.h")]
+# the place-matcher library: once more (its rule header reads no other)
+PLACE_LIB = os.path.join(CSRC, "liblrt_place.so")
+PLACE_STAMP = os.path.join(CSRC, "liblrt_place.srchash")
+PLACE_SOURCES = ["lrt_place.hip"]
+PLACE_HEADERS = ["lrt_place_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_place.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -793,6 +801,46 @@ def build_segment(force: bool = False, verbose: bool = False) -> str:
     return SEGMENT_LIB
 
 
+def place_source_hash() -> str:
+    """source_hash() of the place-matcher library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(PLACE_SOURCES + PLACE_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def place_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(PLACE_LIB):
+        return True
+    try:
+        return open(PLACE_STAMP).read().strip() != place_source_hash()
+    except OSError:
+        return True
+
+
+def build_place(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_place.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other sixteen libraries."""
+    if force or place_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", PLACE_LIB] \
+            + [os.path.join(CSRC, s) for s in PLACE_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(PLACE_STAMP, "w") as f:
+            f.write(place_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(PLACE_LIB)} is up to date (sources {place_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(PLACE_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return PLACE_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -903,6 +951,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_beams(force, verbose)
     build_reg(force, verbose)
     build_segment(force, verbose)
+    build_place(force, verbose)
     return lib
 
 

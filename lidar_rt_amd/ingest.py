@@ -21,7 +21,12 @@ frames are projected first -- the projection never needed the pose -- and ``regi
 identity otherwise), ``sweep_fraction`` to also derive and store the twists from the poses found, and the keyword arguments of
 ``registration.odometry`` (``schedule``, ``huber``, ``lam``, ``min_pairs``, ``tol_t``, ``tol_r``).  ``ingest.json`` gains ``"odometry"``: the
 schedule, every pair's status and final number of partners, and the pairs that kept the constant-velocity guess.  It does not go with
-``compensated``, which needs the twists before the projection.
+``compensated``, which needs the twists before the projection.  Its key ``loop_closure`` (a dict with ``sensor_height`` and, optionally, the keyword
+arguments of ``pose_graph.close_loops``: ``gap``, ``top``, ``max_score``, ``rings``, ``sectors``, ``r_max``, ...) corrects the chain's drift: the
+frames that revisit an earlier place are found (``lidar_rt_amd.place``), verified by an alignment and entered as loop edges of a pose graph over
+the pairs' hessians (``lidar_rt_amd.pose_graph``); the corrected poses go where the chain's went, and ``"odometry"`` gains ``"loop_closure"``
+(the candidates, the accepted and the rejected pairs with the reason, the cost per iteration, and ``closure_error_chain`` / ``closure_error``:
+the largest translation residual of a loop edge under the chain's poses and under the corrected ones).  Without the key nothing changes.
 
 ``discover_actors`` (a dict with ``sensor_height`` and, optionally, the keyword arguments of ``actors.discover``) runs ``lidar_rt_amd.actors.discover`` on
 the projected frames once their poses are known -- given, or found by ``odometry`` -- and writes the moving actors' tracking boxes as ``boxes.npz``
@@ -175,13 +180,26 @@ def _odometry(done, opts, H, W, inc, data_type, sensor2ego, dev) -> dict:
     fraction = opts.pop("sweep_fraction", None)
     make = lambda fr: registration.frame_geometry(torch.from_numpy(np.ascontiguousarray(fr["depth"], np.float32)).to(dev),
                                                   torch.from_numpy(np.ascontiguousarray(fr["mask"])).to(dev), inc, int(H), int(W), data_type, sensor2ego)
-    poses, rep = registration.odometry(_Geometries(done, make), inclination=inc, data_type=data_type, sensor2ego=sensor2ego, **opts)
+    loop = opts.pop("loop_closure", None)
+    if loop is not None and "sensor_height" not in loop:
+        raise ValueError("ingest_point_clouds: loop_closure needs sensor_height (the height of the sensor above the ground, metres)")
+    frames = {int(fr["id"]): make(fr) for fr in done} if loop is not None else _Geometries(done, make)     # the matcher describes all frames in one call
+    poses, rep = registration.odometry(frames, inclination=inc, data_type=data_type, sensor2ego=sensor2ego, **opts, **({"return_steps": True} if loop is not None else {}))
+    closed = None
+    if loop is not None:
+        from . import pose_graph
+        loops, found = pose_graph.close_loops(frames, poses, rep["steps"], inclination=inc, data_type=data_type, sensor2ego=sensor2ego, **loop)
+        poses, solved = pose_graph.optimize(poses, pose_graph.odometry_edges(rep["steps"]) + loops)
+        closed = {**found, "cost": solved["cost"], "iterations": solved["iterations"], "converged": solved["converged"], "loops": solved["loops"],
+                  "closure_error_chain": max((e["before"][0] for e in solved["loops"] if e["kind"] == "loop"), default=None),
+                  "closure_error": max((e["after"][0] for e in solved["loops"] if e["kind"] == "loop"), default=None)}
     twists = sweep.twists_from_poses(poses, fraction) if fraction is not None else None
     for fr in done:
         fr["sensor2world"] = poses[int(fr["id"])]
         if twists is not None:
             fr["twist"] = twists[int(fr["id"])]
-    return {"schedule": rep["schedule"], "pairs": rep["pairs"], "failed": rep["failed"], "first_pose": poses[min(poses)].tolist()}
+    return {"schedule": rep["schedule"], "pairs": rep["pairs"], "failed": rep["failed"], "first_pose": poses[min(poses)].tolist(),
+            **({"loop_closure": closed} if closed is not None else {})}
 
 
 # ---- the command line ------------------------------------------------------------------------------------------------------------------------------------
@@ -271,10 +289,24 @@ def main(argv=None) -> int:
     ap.add_argument("--discover-actors", action="store_true", help="once the poses are known (--poses or --odometry), find the moving actors "
                     "(lidar_rt_amd.actors) and write their tracking boxes as boxes.npz, the report as actors.json; needs --sensor-height")
     ap.add_argument("--sensor-height", type=float, help="--discover-actors: the height of the sensor above the ground [m]")
+    ap.add_argument("--loop-closure", action="store_true", help="--odometry: find the frames that revisit an earlier place (lidar_rt_amd.place), verify them with an "
+                    "alignment and correct the chain with a pose graph (lidar_rt_amd.pose_graph); needs --sensor-height")
+    ap.add_argument("--loop-gap", type=int, default=20, help="--loop-closure: a frame is compared with the frames at least this many before it")
+    ap.add_argument("--loop-top", type=int, default=2, help="--loop-closure: the candidates per frame that are verified")
+    ap.add_argument("--loop-max-score", type=float, default=None, help="--loop-closure: the largest descriptor score (0 identical, 1 disjoint) of a candidate")
+    ap.add_argument("--place-rings", type=int, default=None, help="--loop-closure: the rings of the descriptor (at most 32)")
+    ap.add_argument("--place-sectors", type=int, default=None, help="--loop-closure: the sectors of the descriptor (at most 128 and --width)")
+    ap.add_argument("--place-range", type=float, default=None, help="--loop-closure: the outer ground range of the descriptor [m]")
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None)
     ap.add_argument("--batch", type=int, default=16)
     a = ap.parse_args(argv)
-    if a.discover_actors != (a.sensor_height is not None):
+    if a.loop_closure and not a.odometry:
+        print("ingest: --loop-closure goes with --odometry", file=sys.stderr)
+        return 2
+    if a.loop_closure and a.sensor_height is None:
+        print("ingest: --loop-closure and --sensor-height Z go together", file=sys.stderr)
+        return 2
+    if a.discover_actors != (a.sensor_height is not None) and not (a.loop_closure and not a.discover_actors):
         print("ingest: --discover-actors and --sensor-height Z go together", file=sys.stderr)
         return 2
     if bool(a.poses) == bool(a.odometry):
@@ -320,7 +352,13 @@ def main(argv=None) -> int:
                               max_depth=a.max_depth, test_frames=a.test_frames, device=a.device, batch=a.batch, wrap=not a.no_wrap,
                               notes={"pose_taken_from": borrowed, **({"sweep_fraction": float(a.sweep_fraction)} if a.sweep else {})}, twists=twists,
                               **({"odometry": {**({"first_pose": matrix_file(a.first_pose)} if a.first_pose else {}),
-                                               **({"sweep_fraction": a.sweep_fraction} if a.sweep else {})}} if a.odometry else {}),
+                                               **({"sweep_fraction": a.sweep_fraction} if a.sweep else {}),
+                                               **({"loop_closure": {"sensor_height": a.sensor_height, "gap": a.loop_gap, "top": a.loop_top,
+                                                                    **({"max_score": a.loop_max_score} if a.loop_max_score is not None else {}),
+                                                                    **({"rings": a.place_rings} if a.place_rings is not None else {}),
+                                                                    **({"sectors": a.place_sectors} if a.place_sectors is not None else {}),
+                                                                    **({"r_max": a.place_range} if a.place_range is not None else {})}} if a.loop_closure else {})}}
+                                 if a.odometry else {}),
                               **(dict(compensated=True, sweep_ref=a.sweep_ref, sweep_direction=a.sweep_direction) if a.compensated else {}),
                               **({"discover_actors": {"sensor_height": a.sensor_height}} if a.discover_actors else {}))
     t = rep["total"]
@@ -328,6 +366,7 @@ def main(argv=None) -> int:
     print(f"ingest: {len(ids)} frames, {t['points']} points -> {t['pixels']} pixels ({t['hidden']} hidden, {t['out_of_view']} out of view, {unseen}"
           f"{t['out_of_range']} out of range, {t['invalid']} invalid); " + (f"{len(rep['odometry']['failed'])} of {len(rep['odometry']['pairs'])} pairs kept the constant-velocity guess"
                                                                            if a.odometry else f"{len(borrowed)} frames took an earlier pose")
+          + (f"; {len(rep['odometry']['loop_closure']['accepted'])} loops closed" if a.loop_closure else "")
           + (f"; {rep['actors']['n_actors']} moving actors" if a.discover_actors else "") + f"; wrote {a.out}")
     return 0
 

@@ -505,10 +505,12 @@ def frame_geometry(depth, mask, inclination, H=None, W=None, data_type="KITTI", 
 
 @torch.no_grad()
 def odometry(frames, first_pose=None, schedule=DEFAULT_SCHEDULE, huber=0.1, lam=1e-6, min_pairs=50, tol_t=1e-5, tol_r=1e-6, data_type="KITTI",
-             inclination=None, sensor2ego=None, min_depth=0.0, max_depth=FLT_MAX):
+             inclination=None, sensor2ego=None, min_depth=0.0, max_depth=FLT_MAX, return_steps=False):
     """({id: (4, 4) float64 sensor2world}, report) from ``frames`` = {id: (points, normals, mask)} (``frame_geometry``), see the module text.
     ``first_pose``: the (4, 4) pose of the lowest id (the identity otherwise).  The report: the schedule and, per pair, ``source``, ``target``,
-    ``status`` and the final number of ``partners``; ``failed`` names the source ids whose pair kept the constant-velocity guess."""
+    ``status`` and the final number of ``partners``; ``failed`` names the source ids whose pair kept the constant-velocity guess.  ``return_steps=True`` adds
+    ``report["steps"]``: per pair ``source``, ``target``, ``X`` (3, 4), ``hessian`` (6, 6) and ``status`` as numpy float64, from the same one host read
+    -- the odometry edges of ``pose_graph``."""
     ids = sorted(int(i) for i in frames)
     if len(ids) < 1:
         raise RegistrationError("odometry: no frames")
@@ -530,10 +532,14 @@ def odometry(frames, first_pose=None, schedule=DEFAULT_SCHEDULE, huber=0.1, lam=
         X = torch.stack([r.X for r in steps]).cpu().numpy()
         status = torch.stack([r.status for r in steps]).cpu().numpy()
         partners = torch.stack([r.log[-1, 0] for r in steps]).cpu().numpy()
+        hessian = torch.stack([r.hessian for r in steps]).cpu().numpy() if return_steps else None
         for k, (a, b) in enumerate(zip(ids[:-1], ids[1:])):
             step = np.eye(4)
             step[:3] = X[k]
             poses[b] = poses[a] @ step
             pairs.append({"source": b, "target": a, "status": int(status[k]), "partners": int(partners[k])})
     report = {"schedule": sched.tolist(), "huber": float(huber), "pairs": pairs, "failed": [p["source"] for p in pairs if p["status"] in (FEW, PIVOT)]}
+    if return_steps:
+        report["steps"] = [{"source": p["source"], "target": p["target"], "X": X[k].copy(), "hessian": hessian[k].copy(), "status": p["status"]}
+                           for k, p in enumerate(pairs)]
     return poses, report
