@@ -58,6 +58,9 @@
 * ``csrc/liblrt_place.so`` -- the place matcher: one ring-by-sector descriptor per scan and every scan against every earlier scan at every yaw
   (``csrc/lrt_place.hip``, C ABI ``include/lrt_place.h``): a seventeenth product library on the same pattern.  Loaded by ``lidar_rt_amd.place``.
 
+* ``csrc/liblrt_mesh.so`` -- surface meshes from range images: projective TSDF fusion and marching cubes (``csrc/lrt_mesh.hip``, C ABI
+  ``include/lrt_mesh.h``): an eighteenth product library on the same pattern.  Loaded by ``lidar_rt_amd.mesh``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -173,6 +176,11 @@ PLACE_LIB = os.path.join(CSRC, "liblrt_place.so")
 PLACE_STAMP = os.path.join(CSRC, "liblrt_place.srchash")
 PLACE_SOURCES = ["lrt_place.hip"]
 PLACE_HEADERS = ["lrt_place_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_place.h")]
+# the mesh library: once more (it reads the projection's rule header, as it is, and its generated triangle table)
+MESH_LIB = os.path.join(CSRC, "liblrt_mesh.so")
+MESH_STAMP = os.path.join(CSRC, "liblrt_mesh.srchash")
+MESH_SOURCES = ["lrt_mesh.hip"]
+MESH_HEADERS = ["lrt_mesh_math.h", "lrt_mesh_tables.h", "lrt_project_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_mesh.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -841,6 +849,46 @@ def build_place(force: bool = False, verbose: bool = False) -> str:
     return PLACE_LIB
 
 
+def mesh_source_hash() -> str:
+    """source_hash() of the mesh library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(MESH_SOURCES + MESH_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def mesh_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(MESH_LIB):
+        return True
+    try:
+        return open(MESH_STAMP).read().strip() != mesh_source_hash()
+    except OSError:
+        return True
+
+
+def build_mesh(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_mesh.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other seventeen libraries."""
+    if force or mesh_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", MESH_LIB] \
+            + [os.path.join(CSRC, s) for s in MESH_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(MESH_STAMP, "w") as f:
+            f.write(mesh_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(MESH_LIB)} is up to date (sources {mesh_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(MESH_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return MESH_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -952,6 +1000,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_reg(force, verbose)
     build_segment(force, verbose)
     build_place(force, verbose)
+    build_mesh(force, verbose)
     return lib
 
 
