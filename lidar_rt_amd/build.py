@@ -61,6 +61,9 @@
 * ``csrc/liblrt_mesh.so`` -- surface meshes from range images: projective TSDF fusion and marching cubes (``csrc/lrt_mesh.hip``, C ABI
   ``include/lrt_mesh.h``): an eighteenth product library on the same pattern.  Loaded by ``lidar_rt_amd.mesh``.
 
+* ``csrc/liblrt_raycast.so`` -- range images of a fused TSDF grid: one marching ray per lane (``csrc/lrt_raycast.hip``, C ABI
+  ``include/lrt_raycast.h``): a nineteenth product library on the same pattern.  Loaded by ``lidar_rt_amd.raycast``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -181,6 +184,11 @@ MESH_LIB = os.path.join(CSRC, "liblrt_mesh.so")
 MESH_STAMP = os.path.join(CSRC, "liblrt_mesh.srchash")
 MESH_SOURCES = ["lrt_mesh.hip"]
 MESH_HEADERS = ["lrt_mesh_math.h", "lrt_mesh_tables.h", "lrt_project_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_mesh.h")]
+# the ray-casting library: once more (its rule header reads no other)
+RAYCAST_LIB = os.path.join(CSRC, "liblrt_raycast.so")
+RAYCAST_STAMP = os.path.join(CSRC, "liblrt_raycast.srchash")
+RAYCAST_SOURCES = ["lrt_raycast.hip"]
+RAYCAST_HEADERS = ["lrt_raycast_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_raycast.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -889,6 +897,46 @@ def build_mesh(force: bool = False, verbose: bool = False) -> str:
     return MESH_LIB
 
 
+def raycast_source_hash() -> str:
+    """source_hash() of the ray-casting library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(RAYCAST_SOURCES + RAYCAST_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def raycast_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(RAYCAST_LIB):
+        return True
+    try:
+        return open(RAYCAST_STAMP).read().strip() != raycast_source_hash()
+    except OSError:
+        return True
+
+
+def build_raycast(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_raycast.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other eighteen libraries."""
+    if force or raycast_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", RAYCAST_LIB] \
+            + [os.path.join(CSRC, s) for s in RAYCAST_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(RAYCAST_STAMP, "w") as f:
+            f.write(raycast_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(RAYCAST_LIB)} is up to date (sources {raycast_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(RAYCAST_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return RAYCAST_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -1001,6 +1049,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_segment(force, verbose)
     build_place(force, verbose)
     build_mesh(force, verbose)
+    build_raycast(force, verbose)
     return lib
 
 
