@@ -223,7 +223,11 @@ int lrt_status_to_device(lrt_state* st, float* dst, void* stream);
  *                    replica forms bit-identical sums).  zero_only = 1: the rows of all lists are cleared (a caller that keeps its
  *                    gradient buffers zero between steps: option "grads_prezeroed").  status (device, 1 + N words, may be NULL):
  *                    [0] |= 1 when a list did not fit `cap` (its blocks are skipped: the step's sums are incomplete), [1 + r] = length
- *                    of list r.  No call reads anything back: the caller looks at `status` when it has arrived. */
+ *                    of list r (written with zero_only = 0 only).  A block is skipped when off[b] + n[b] > cap in ANY of the N lists:
+ *                    with zero_only = 0 none of its rows is read or written, the own list's included.  zero_only = 1 skips nothing:
+ *                    in such a block too it clears the entries that fitted (the first min(n[b], cap - off[b]) of the block, none
+ *                    when off[b] >= cap -- the only ones a message holds) and raises [0] all the same.
+ *                    No call reads anything back: the caller looks at `status` when it has arrived. */
 long long lrt_xchg_msg_words(int P, int M, int cap, int with_rows);
 int lrt_xchg_pack(int device, int P, int M, int cap, const float* d_means, const float* d_scales, const float* d_rotations, const float* d_opacities,
                   const float* d_shs, const float* accum, int32_t* msg, unsigned* counters, int parity, int with_rows, void* stream);

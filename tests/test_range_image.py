@@ -35,7 +35,7 @@ def test_the_library_has_a_source_list_of_its_own_and_moves_no_other_hash():
               + lrt_build.DENSIFY_SOURCES + lrt_build.DENSIFY_HEADERS)
     assert not any("lrt_project" in f for f in others)
     # the other libraries' hashes at the commit this library was added on: committed profiles are keyed by them
-    assert lrt_build.source_hash() == "aa80398d770ab91f"          # moved once since, by the non-finite-input fixes in lrt_chamfer.hip
+    assert lrt_build.source_hash() == "2c98b54882a7ff74"          # moved twice since: the non-finite-input fixes in lrt_chamfer.hip; a comment of include/lrt.h (lrt_xchg_apply, zero_only on an overflowed block)
     assert lrt_build.loss_source_hash() == "cc56b0c83f72d5ca"
     assert lrt_build.gridcd_source_hash() == "fd279d9f7ff67722"
     assert lrt_build.init_source_hash() == "0fd7105f5d08ab22"
