@@ -64,6 +64,9 @@
 * ``csrc/liblrt_raycast.so`` -- range images of a fused TSDF grid: one marching ray per lane (``csrc/lrt_raycast.hip``, C ABI
   ``include/lrt_raycast.h``): a nineteenth product library on the same pattern.  Loaded by ``lidar_rt_amd.raycast``.
 
+* ``csrc/liblrt_sweepfuse.so`` -- TSDF fusion of range images of a moving sensor: every voxel centre under the sweep model (``csrc/lrt_sweepfuse.hip``,
+  C ABI ``include/lrt_sweepfuse.h``): a twentieth product library on the same pattern.  Loaded by ``lidar_rt_amd.sweep_fuse``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -189,6 +192,12 @@ RAYCAST_LIB = os.path.join(CSRC, "liblrt_raycast.so")
 RAYCAST_STAMP = os.path.join(CSRC, "liblrt_raycast.srchash")
 RAYCAST_SOURCES = ["lrt_raycast.hip"]
 RAYCAST_HEADERS = ["lrt_raycast_math.h", "lrt_device_guard.h", os.path.join("..", "..", "include", "lrt_raycast.h")]
+# the sweep-fusion library: once more (it reads the rule headers of the mesh, the projection and the two sweep libraries; their hashes do not read back)
+SWEEPFUSE_LIB = os.path.join(CSRC, "liblrt_sweepfuse.so")
+SWEEPFUSE_STAMP = os.path.join(CSRC, "liblrt_sweepfuse.srchash")
+SWEEPFUSE_SOURCES = ["lrt_sweepfuse.hip"]
+SWEEPFUSE_HEADERS = ["lrt_sweepfuse_math.h", "lrt_mesh_math.h", "lrt_sweepproj_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h",
+                     os.path.join("..", "..", "include", "lrt_sweepfuse.h")]
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -937,6 +946,46 @@ def build_raycast(force: bool = False, verbose: bool = False) -> str:
     return RAYCAST_LIB
 
 
+def sweepfuse_source_hash() -> str:
+    """source_hash() of the sweep-fusion library: over ITS sources, headers and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(SWEEPFUSE_SOURCES + SWEEPFUSE_HEADERS):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def sweepfuse_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(SWEEPFUSE_LIB):
+        return True
+    try:
+        return open(SWEEPFUSE_STAMP).read().strip() != sweepfuse_source_hash()
+    except OSError:
+        return True
+
+
+def build_sweepfuse(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_sweepfuse.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other nineteen libraries."""
+    if force or sweepfuse_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", SWEEPFUSE_LIB] \
+            + [os.path.join(CSRC, s) for s in SWEEPFUSE_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(SWEEPFUSE_STAMP, "w") as f:
+            f.write(sweepfuse_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(SWEEPFUSE_LIB)} is up to date (sources {sweepfuse_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(SWEEPFUSE_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return SWEEPFUSE_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -1050,6 +1099,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_place(force, verbose)
     build_mesh(force, verbose)
     build_raycast(force, verbose)
+    build_sweepfuse(force, verbose)
     return lib
 
 

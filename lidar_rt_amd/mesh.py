@@ -6,6 +6,10 @@
     write_ply(path, mesh); ply = read_ply(path)                               # binary little-endian, world x y z as doubles
 
     python -m lidar_rt_amd.mesh --data DIR --out mesh.ply [--voxel 0.1] [--trunc M] [--frames train|test|all] [--static-only] [--device cpu]
+                                [--sweep stored [--sweep-ref 0.5] [--sweep-direction cw]]
+
+``--sweep stored`` fuses under the sweep model: each frame's stored twist (and column times) through ``sweep_fuse.integrate_sweep``, so that the
+motion of the sensor within a sweep does not shear the surface.
 
 ``include/lrt_mesh.h`` states every rule and ``csrc/lrt_mesh_math.h`` is its text for the device and the host.
 
@@ -618,11 +622,16 @@ def _quat_rotation(q):
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
-def load_frames(root, which="train", static_only=False):
+def load_frames(root, which="train", static_only=False, sweep="off", sweep_ref=0.5, sweep_direction="cw"):
     """The frames of a sequence directory for fusion: (meta, [dict(id, depth, intensity, mask, sensor2world float64, world points, valid,
     excluded)], inclination).  ``static_only``: the valid pixels whose return lies inside a tracking box present in that frame are excluded
-    (``scene_init.assign_to_boxes``'s rule)."""
-    from . import scene_init, sweep
+    (``scene_init.assign_to_boxes``'s rule).  ``sweep="stored"``: every frame also carries its ``twist`` (6,) and ``tau`` (W,) float64 from its
+    file, as ``sequence.load_sequence(sweep="stored")`` reads them (a frame without a twist is refused with its file's name; one without column
+    times takes ``sweep.column_times(W, sweep_ref, sweep_direction)``), and its world points are ``sweep_fuse.sweep_points``'s."""
+    from . import scene_init
+    from . import sweep as sweep_mod
+    if sweep not in ("off", "stored"):
+        raise MeshError(f"load_frames: sweep {sweep!r} ('off' or 'stored')")
     with open(os.path.join(root, "meta.json")) as f:
         meta = json.load(f)
     test = [int(t) for t in meta.get("test_frames", [])]
@@ -641,7 +650,7 @@ def load_frames(root, which="train", static_only=False):
         inc = z["inclination"].astype(np.float64).reshape(-1)
         if inc0 is None:
             inc0 = inc
-            d = sweep.sweep_rays(torch.eye(4, dtype=torch.float32)[:3].contiguous(), None, int(meta["height"]), int(meta["width"]),
+            d = sweep_mod.sweep_rays(torch.eye(4, dtype=torch.float32)[:3].contiguous(), None, int(meta["height"]), int(meta["width"]),
                                  inc.tolist() if inc.size > 2 else (float(inc[0]), float(inc[1])), meta["data_type"],
                                  None if s2e is None else torch.as_tensor(s2e, dtype=torch.float32))[1]
             dirs = d.numpy().astype(np.float64)
@@ -651,7 +660,20 @@ def load_frames(root, which="train", static_only=False):
         mask = z["mask"].astype(bool)
         S = z["sensor2world"].astype(np.float64).reshape(4, 4)
         valid = mask & (depth > 0)
-        world = (dirs * depth[..., None].astype(np.float64)) @ S[:3, :3].T + S[:3, 3]
+        motion = {}
+        if sweep == "stored":
+            from . import sweep_fuse
+            path = os.path.join(root, "frames", f"{fid:06d}.npz")
+            if "twist" not in z.files:
+                raise MeshError(f"{path}: no stored twist (--sweep stored needs one per frame)")
+            try:
+                tau = z["tau"].astype(np.float64).reshape(-1) if "tau" in z.files else sweep_mod.column_times(int(meta["width"]), sweep_ref, sweep_direction).numpy()
+            except sweep_mod.SweepError as e:
+                raise MeshError(str(e)) from None
+            motion = dict(twist=z["twist"].astype(np.float64).reshape(6), tau=tau)
+            world = sweep_fuse.sweep_points(depth, S, motion["twist"], inc, meta["data_type"], s2e, tau=tau)
+        else:
+            world = (dirs * depth[..., None].astype(np.float64)) @ S[:3, :3].T + S[:3, 3]
         excluded = np.zeros_like(valid)
         if boxes is not None and fid in [int(x) for x in boxes["frames"]]:
             k = [int(x) for x in boxes["frames"]].index(fid)
@@ -662,8 +684,39 @@ def load_frames(root, which="train", static_only=False):
                                                          torch.from_numpy(boxes["valid"][:, k].reshape(A)))[0].numpy()
             excluded = valid & (label > 0)
         out.append(dict(id=fid, depth=depth, intensity=z["intensity"].astype(np.float32), mask=valid & ~excluded, sensor2world=S, world=world,
-                        valid=int(valid.sum()), excluded=int(excluded.sum())))
+                        valid=int(valid.sum()), excluded=int(excluded.sum()), **motion))
     return meta, out, inc0
+
+
+def fuse_frames(grid, frames, inc, meta, batch, max_depth, sweep="off"):
+    """Fuse the frames ``load_frames`` returned into ``grid``, ``batch`` frames per call.  ``sweep="stored"``: through ``sweep_fuse.integrate_sweep``
+    with the frames' twists; a call takes frames of one ``tau``, so a batch ends where the column times change.  Returns None, or with the CPU twin
+    of the sweep fusion dict(unseen, fused) summed over the calls."""
+    dev = grid.device
+    s2e = meta.get("sensor2ego")
+    s2e = None if s2e is None else np.asarray(s2e, np.float64)
+    incl = inc if inc.size > 2 else (float(inc[0]), float(inc[1]))
+    counts = None
+    b = 0
+    while b < len(frames):
+        e = min(b + batch, len(frames))
+        if sweep == "stored":
+            e = next((k for k in range(b + 1, e) if not np.array_equal(frames[k]["tau"], frames[b]["tau"])), e)
+        chunk = frames[b:e]
+        st = lambda k, dt: torch.from_numpy(np.stack([f[k] for f in chunk]).astype(dt)).to(dev)
+        args = (grid, st("depth", np.float32), st("mask", np.bool_), np.stack([f["sensor2world"] for f in chunk]), incl)
+        if sweep == "stored":
+            from . import sweep_fuse
+            r = sweep_fuse.integrate_sweep(*args, np.stack([f["twist"] for f in chunk]), meta["data_type"], s2e, st("intensity", np.float32), 0.0,
+                                           max_depth, tau=chunk[0]["tau"])
+            if r is not None:
+                counts = counts or {"unseen": 0, "fused": 0}
+                counts["unseen"] += r.unseen
+                counts["fused"] += r.fused
+        else:
+            integrate(*args, meta["data_type"], s2e, st("intensity", np.float32), 0.0, max_depth)
+        b = e
+    return counts
 
 
 def grid_bounds(frames, voxel, trunc, bounds=None):
@@ -687,7 +740,8 @@ def grid_bounds(frames, voxel, trunc, bounds=None):
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m lidar_rt_amd.mesh", description=(
         "Fuse a sequence's range images into a TSDF grid (projective: every voxel into every image) and extract its surface by marching cubes. "
-        "Frames are fused with their per-frame poses; the rolling-shutter shear of a moving sensor (train --sweep) is NOT compensated."))
+        "Frames are fused with one pose per frame (--sweep off), or under the sweep model with each frame's stored twist (--sweep stored), which "
+        "compensates the rolling-shutter shear of a moving sensor (train --sweep)."))
     ap.add_argument("--data", required=True, help="a sequence directory (lidar_rt_amd.sequence)")
     ap.add_argument("--out", default="mesh.ply", help="the PLY to write; mesh.json goes next to it")
     ap.add_argument("--voxel", type=float, default=0.1)
@@ -700,13 +754,21 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16, help="frames per integrate call")
     ap.add_argument("--static-only", action="store_true", help="drop the returns inside a tracking box present in their frame")
     ap.add_argument("--device", default="cuda", help="cuda (the library) or cpu (the numpy twins)")
+    ap.add_argument("--sweep", choices=("off", "stored"), default="off", help="stored: fuse under the sweep model with each frame's stored twist (sweep_fuse.integrate_sweep)")
+    ap.add_argument("--sweep-ref", type=float, default=0.5, help="--sweep: the part of the sweep at which a frame's pose holds, for frames that store no column times")
+    ap.add_argument("--sweep-direction", choices=("cw", "ccw"), default="cw", help="--sweep: cw = time rises with the column index, for frames that store no column times")
     a = ap.parse_args(argv)
     t0 = time.perf_counter()
     voxel = float(a.voxel)
     trunc = 3.0 * voxel if a.trunc is None else float(a.trunc)
     if a.batch < 1:
         raise SystemExit("--batch must be at least 1")
-    meta, frames, inc = load_frames(a.data, a.frames, a.static_only)
+    try:
+        meta, frames, inc = load_frames(a.data, a.frames, a.static_only, a.sweep, a.sweep_ref, a.sweep_direction)
+    except MeshError as e:
+        if a.sweep == "off":
+            raise
+        raise SystemExit(str(e)) from None
     origin, dims = grid_bounds(frames, voxel, trunc, a.bounds)
     n = math.prod(dims)
     if n > a.max_voxels:
@@ -714,13 +776,7 @@ def main(argv=None):
                          "raise --max-voxels, give --bounds or a coarser --voxel")
     dev = torch.device(a.device)
     grid = TsdfGrid(origin, voxel, dims, trunc, dev, intensity=True)
-    s2e = meta.get("sensor2ego")
-    for b in range(0, len(frames), a.batch):
-        chunk = frames[b:b + a.batch]
-        st = lambda k, dt: torch.from_numpy(np.stack([f[k] for f in chunk]).astype(dt)).to(dev)
-        integrate(grid, st("depth", np.float32), st("mask", np.bool_), np.stack([f["sensor2world"] for f in chunk]),
-                  inc if inc.size > 2 else (float(inc[0]), float(inc[1])), meta["data_type"], None if s2e is None else np.asarray(s2e, np.float64),
-                  st("intensity", np.float32), 0.0, a.max_depth)
+    counts = fuse_frames(grid, frames, inc, meta, a.batch, a.max_depth, a.sweep)
     mesh = extract(grid, a.min_weight)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     write_ply(a.out, mesh)
@@ -728,6 +784,7 @@ def main(argv=None):
               "frames": [f["id"] for f in frames], "pixels": {str(f["id"]): {"valid": f["valid"], "excluded": f["excluded"]} for f in frames},
               "totals": {"vertices": int(mesh.vertices.shape[0]), "faces": int(mesh.faces.shape[0]), "observed_voxels": int((grid.weight > 0).sum()),
                          "voxels": n, "seconds": round(time.perf_counter() - t0, 3)}}
+    report["sweep"] = {"mode": a.sweep, **(counts or {})}
     with open(os.path.join(os.path.dirname(os.path.abspath(a.out)), "mesh.json"), "w") as f:
         json.dump(report, f, indent=1)
     print(json.dumps(report["totals"]))

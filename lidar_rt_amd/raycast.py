@@ -17,6 +17,8 @@
   ``raycast_reference``, the numpy float64 twin, equal to the device bit for bit in depth, hit, intensity and samples.
 * ``render_frames`` casts a sensor's own rays, so a sweep (``--sweep stored``) or a beam table applies as it does to ``evaluate``; its output goes to
   ``metrics.frame_metrics`` and ``simulate.clouds_from_renders`` as it is.
+* ``--fuse-sweep stored`` FUSES under the sweep model (``sweep_fuse.integrate_sweep`` with each fused frame's stored twist), so that the grid is
+  not sheared by the sensor's motion within a sweep; ``--sweep stored`` is how the rays are cast and does not imply it.
 """
 from __future__ import annotations
 
@@ -314,6 +316,10 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16, help="frames per integrate call")
     ap.add_argument("--static-only", action="store_true", help="fuse without the returns inside a tracking box present in their frame")
     ap.add_argument("--sweep", choices=("off", "stored"), default="off", help="cast with one pose per column (each frame's stored twist), as evaluate --sweep")
+    ap.add_argument("--fuse-sweep", choices=("off", "stored"), default="off",
+                    help="stored: fuse under the sweep model with each fused frame's stored twist (sweep_fuse.integrate_sweep); --sweep does not imply it")
+    ap.add_argument("--sweep-ref", type=float, default=0.5, help="the part of the sweep at which a frame's pose holds, for frames that store no column times")
+    ap.add_argument("--sweep-direction", choices=("cw", "ccw"), default="cw", help="cw = time rises with the column index, for frames that store no column times")
     ap.add_argument("--beams", default=None, metavar="FILE", help="cast through a beam table (lidar_rt_amd.beams), as evaluate --beams")
     ap.add_argument("--raydrop-ratio", type=float, default=0.4)
     ap.add_argument("--use-gt-mask", action="store_true", help="mask the renders with the ground-truth ray-hit mask instead of the hit mask")
@@ -327,7 +333,12 @@ def main(argv=None):
     if a.batch < 1:
         raise SystemExit("--batch must be at least 1")
     dev = torch.device(a.device)
-    meta, frames, inc = mesh.load_frames(a.data, a.fuse, a.static_only)
+    try:
+        meta, frames, inc = mesh.load_frames(a.data, a.fuse, a.static_only, a.fuse_sweep, a.sweep_ref, a.sweep_direction)
+    except mesh.MeshError as e:
+        if a.fuse_sweep == "off":
+            raise
+        raise SystemExit(str(e)) from None
     origin, dims = mesh.grid_bounds(frames, voxel, trunc, a.bounds)
     nvox = math.prod(dims)
     if nvox > a.max_voxels:
@@ -340,16 +351,11 @@ def main(argv=None):
     except RaycastError as e:
         raise SystemExit(str(e)) from None
     s2e = meta.get("sensor2ego")
-    for b in range(0, len(frames), a.batch):
-        chunk = frames[b:b + a.batch]
-        st = lambda k, dt: torch.from_numpy(np.stack([f[k] for f in chunk]).astype(dt)).to(dev)
-        mesh.integrate(grid, st("depth", np.float32), st("mask", np.bool_), np.stack([f["sensor2world"] for f in chunk]),
-                       inc if inc.size > 2 else (float(inc[0]), float(inc[1])), meta["data_type"], None if s2e is None else np.asarray(s2e, np.float64),
-                       st("intensity", np.float32), 0.0, a.max_depth)
+    fuse_counts = mesh.fuse_frames(grid, frames, inc, meta, a.batch, a.max_depth, a.fuse_sweep)
     # the rays are formed on the host whatever the device: a device's sin and cos may differ from the host's in the last bit, and with the same
     # rays and the same grid the cast writes the same bytes on both
     host = torch.device("cpu")
-    seq = sequence_mod.load_sequence(a.data, host, sweep=a.sweep)
+    seq = sequence_mod.load_sequence(a.data, host, sweep=a.sweep, sweep_ref=a.sweep_ref, sweep_direction=a.sweep_direction)
     if a.beams:
         beam_rows = int(next(iter(seq.frames.depth.values())).shape[0])
         beams_mod.apply_table(seq.frames, beams_mod.load_table(a.beams, beam_rows, host))
@@ -391,7 +397,7 @@ def main(argv=None):
         sequence_mod.write_sequence(a.sequence, out_rows, data_type=meta["data_type"], extent=float(meta.get("extent", 1.0)), sensor2ego=s2e)
     report = {"frames": ids, "mean": mean, "per_frame": per_frame,
               "grid": {"origin": [float(x) for x in origin], "voxel": voxel, "dims": list(dims), "trunc": trunc, "observed_voxels": int((grid.weight > 0).sum())},
-              "fused_frames": [f["id"] for f in frames],
+              "fused_frames": [f["id"] for f in frames], "fuse_sweep": {"mode": a.fuse_sweep, **(fuse_counts or {})},
               "cast": {"min_weight": p[0], "step": p[1], "far_step": p[2], "max_depth": p[4], "rays": nrays, "hit_fraction": hits / nrays if nrays else 0.0,
                        "samples_per_ray": {"mean": spr / nrays if nrays else 0.0, "max": smax}},
               "seconds": round(time.perf_counter() - t0, 3), "args": vars(a)}
