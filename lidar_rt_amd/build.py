@@ -67,6 +67,10 @@
 * ``csrc/liblrt_sweepfuse.so`` -- TSDF fusion of range images of a moving sensor: every voxel centre under the sweep model (``csrc/lrt_sweepfuse.hip``,
   C ABI ``include/lrt_sweepfuse.h``): a twentieth product library on the same pattern.  Loaded by ``lidar_rt_amd.sweep_fuse``.
 
+* ``csrc/liblrt_mapreg.so`` -- scan-to-map registration: range images aligned to the fused TSDF grid, one trilinear sample per pixel
+  (``csrc/lrt_mapreg.hip``, C ABI ``include/lrt_mapreg.h``): a twenty-first product library on the same pattern.  Loaded by
+  ``lidar_rt_amd.map_registration``.
+
 ``python -m lidar_rt_amd.build`` rebuilds what is stale (``--force``: everything).
 """
 from __future__ import annotations
@@ -198,6 +202,12 @@ SWEEPFUSE_STAMP = os.path.join(CSRC, "liblrt_sweepfuse.srchash")
 SWEEPFUSE_SOURCES = ["lrt_sweepfuse.hip"]
 SWEEPFUSE_HEADERS = ["lrt_sweepfuse_math.h", "lrt_mesh_math.h", "lrt_sweepproj_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h",
                      os.path.join("..", "..", "include", "lrt_sweepfuse.h")]
+MAPREG_LIB = os.path.join(CSRC, "liblrt_mapreg.so")
+MAPREG_STAMP = os.path.join(CSRC, "liblrt_mapreg.srchash")
+MAPREG_SOURCES = ["lrt_mapreg.hip"]
+MAPREG_HEADERS = ["lrt_mapreg_math.h", "lrt_raycast_math.h", "lrt_project_math.h", "lrt_sweep_math.h", "lrt_device_guard.h",
+                  os.path.join("..", "..", "include", "lrt_mapreg.h")]
+MAPREG_BORROWED = ["lrt_reg_math.h"]     # the registration's rule header, included as it is: hashed here, listed with liblrt_reg.so's own files only
 
 
 def is_stale(lib: str = LIB, stamp: str = STAMP) -> bool:
@@ -986,6 +996,46 @@ def build_sweepfuse(force: bool = False, verbose: bool = False) -> str:
     return SWEEPFUSE_LIB
 
 
+def mapreg_source_hash() -> str:
+    """source_hash() of the scan-to-map registration library: over ITS sources, headers, the borrowed rule header and the code-generation flags."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in sorted(MAPREG_SOURCES + MAPREG_HEADERS + MAPREG_BORROWED):
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(f.encode()); h.update(fh.read())
+    h.update(" ".join(CODEGEN_FLAGS).encode())
+    return h.hexdigest()[:16]
+
+
+def mapreg_is_stale() -> bool:
+    """Missing, or compiled from other sources (the content hash stamped next to it; no stamp = rebuilt)."""
+    if not os.path.exists(MAPREG_LIB):
+        return True
+    try:
+        return open(MAPREG_STAMP).read().strip() != mapreg_source_hash()
+    except OSError:
+        return True
+
+
+def build_mapreg(force: bool = False, verbose: bool = False) -> str:
+    """liblrt_mapreg.so, compiled when stale; the resource gate runs on it on EVERY call, as on the other twenty libraries."""
+    if force or mapreg_is_stale():
+        cmd = [hipcc_path(), f"--offload-arch={ARCH}"] + CODEGEN_FLAGS + ["-std=c++17", "-fPIC", "-shared", "-o", MAPREG_LIB] \
+            + [os.path.join(CSRC, s) for s in MAPREG_SOURCES]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd, cwd=CSRC)
+        with open(MAPREG_STAMP, "w") as f:
+            f.write(mapreg_source_hash() + "\n")
+    elif verbose:
+        print(f"{os.path.basename(MAPREG_LIB)} is up to date (sources {mapreg_source_hash()}): not recompiled (--force compiles anyway)", flush=True)
+    from . import resources
+    res = resources.check(MAPREG_LIB)
+    if verbose:
+        print(resources.table_md(res), flush=True)
+    return MAPREG_LIB
+
+
 EXT_SRC = os.path.join(CSRC, "lrt_torch_ext.cpp")
 EXT_DIR = os.path.join(HERE, "diff_lidar_tracer")
 
@@ -1100,6 +1150,7 @@ def _build_product(force: bool, verbose: bool) -> str:
     build_mesh(force, verbose)
     build_raycast(force, verbose)
     build_sweepfuse(force, verbose)
+    build_mapreg(force, verbose)
     return lib
 
 

@@ -27,6 +27,11 @@ frames that revisit an earlier place are found (``lidar_rt_amd.place``), verifie
 the pairs' hessians (``lidar_rt_amd.pose_graph``); the corrected poses go where the chain's went, and ``"odometry"`` gains ``"loop_closure"``
 (the candidates, the accepted and the rejected pairs with the reason, the cost per iteration, and ``closure_error_chain`` / ``closure_error``:
 the largest translation residual of a loop edge under the chain's poses and under the corrected ones).  Without the key nothing changes.
+Its key ``map_tracking`` (a dict, possibly empty: ``voxel`` [0.2 m], ``trunc`` [4 voxels], ``max_voxels`` and the keyword arguments of
+``map_registration.track_and_fuse``: ``iters``, ``huber``, ``lam``, ``min_pairs``, ``tol_t``, ``tol_r``, ``min_weight``) runs the chain first, sizes a
+TSDF grid from the chain's poses (``mesh.grid_bounds``) and tracks every frame against everything fused so far
+(``lidar_rt_amd.map_registration``), started from the chain's steps; the tracked poses go where the chain's went and ``ingest.json`` gains
+``"map_tracking"``.  It does not go with ``loop_closure``.  The range image must be fine enough for the map (``map_registration``'s module text).
 
 ``discover_actors`` (a dict with ``sensor_height`` and, optionally, the keyword arguments of ``actors.discover``) runs ``lidar_rt_amd.actors.discover`` on
 the projected frames once their poses are known -- given, or found by ``odometry`` -- and writes the moving actors' tracking boxes as ``boxes.npz``
@@ -34,6 +39,7 @@ and the report as ``actors.json``: what ``python -m lidar_rt_amd.actors`` adds t
 
     python -m lidar_rt_amd.ingest --points DIR --poses FILE --out DIR --height 66 --width 1030 --inclination -0.4346 0.0349
     python -m lidar_rt_amd.ingest --points DIR --odometry --out DIR --height 66 --width 1030 --inclination -0.4346 0.0349
+    python -m lidar_rt_amd.ingest --points DIR --odometry --map-tracking [--map-voxel 0.2] [--map-trunc 0.8] --out DIR --height 66 --width 1030 ...
     python -m lidar_rt_amd.ingest --points DIR --odometry --discover-actors --sensor-height 1.8 --out DIR --height 66 --width 1030 --inclination ...
 
 ``--points DIR`` holds ``<id>.npy`` ``(N, 4)`` or KITTI-style ``<id>.bin`` (float32 quadruples), ids being integers.  ``--poses FILE`` is a ``.npy``
@@ -134,7 +140,8 @@ def ingest_point_clouds(out_dir: str, clouds: Iterable, H: int, W: int, inclinat
 
     done = list(frames())                                                    # every image first: the extent is known after the last one
     if odometry is not None:
-        notes = {**(notes or {}), "odometry": _odometry(done, dict(odometry), H, W, inc, data_type, sensor2ego, dev)}
+        entry, tracking = _odometry(done, dict(odometry), H, W, inc, data_type, sensor2ego, dev, max_depth)
+        notes = {**(notes or {}), "odometry": entry, **({"map_tracking": tracking} if tracking is not None else {})}
     actors_report = None
     if discover_actors is not None:
         from . import actors
@@ -174,17 +181,56 @@ class _Geometries:
         return self.kept[i]
 
 
-def _odometry(done, opts, H, W, inc, data_type, sensor2ego, dev) -> dict:
-    """Poses (and, with ``sweep_fraction``, twists) for the projected frames ``done``, in place; returns the report's entry."""
+def _map_tracking(done, opts, frames, poses, steps, inc, data_type, sensor2ego, dev, max_depth):
+    """The chain's poses replaced by poses tracked against the grid of everything fused so far: ({id: (4, 4)}, the report's entry)."""
+    from . import map_registration, mesh
+    voxel = float(opts.pop("voxel", 0.2))
+    trunc = opts.pop("trunc", None)
+    trunc = 4.0 * voxel if trunc is None else float(trunc)
+    max_voxels = int(opts.pop("max_voxels", mesh.DEFAULT_MAX_VOXELS))
+    if not (voxel > 0.0 and trunc > 0.0):
+        raise ValueError(f"ingest_point_clouds: map_tracking voxel {voxel}, trunc {trunc} (both positive)")
+    corners = []
+    for i in sorted(poses):                                                 # the extent of every frame's returns under the chain's poses
+        pts, _, mask = frames[i]
+        p = pts[mask].detach().cpu().numpy().astype(np.float64) @ poses[i][:3, :3].T + poses[i][:3, 3]
+        if len(p):
+            corners.append(dict(world=np.stack([p.min(0), p.max(0)]), mask=np.ones(2, bool)))
+    try:
+        origin, dims = mesh.grid_bounds(corners, voxel, trunc)
+    except mesh.MeshError as e:
+        raise ValueError(f"ingest_point_clouds: map_tracking: {e}") from None
+    if int(np.prod(dims)) > max_voxels:
+        raise ValueError(f"ingest_point_clouds: map_tracking needs a grid of {dims[0]} x {dims[1]} x {dims[2]} voxels at voxel {voxel}, more than "
+                         f"max_voxels {max_voxels}: a coarser voxel, or fewer frames")
+    grid = mesh.TsdfGrid(origin, voxel, dims, trunc, dev, intensity=False)
+    by_id = {int(fr["id"]): fr for fr in done}
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
+    images = {i: (up(fr["depth"], np.float32), up(fr["mask"], np.bool_)) for i, fr in by_id.items()}
+    rel = {int(s["source"]): np.vstack([s["X"], [0.0, 0.0, 0.0, 1.0]]) for s in steps}
+    tracked, rep = map_registration.track_and_fuse(grid, frames, images, first_pose=poses[min(poses)], steps=rel, inclination=inc, data_type=data_type,
+                                                   sensor2ego=sensor2ego, max_depth=max_depth, **opts)
+    moved = {i: float(np.linalg.norm(tracked[i][:3, 3] - poses[i][:3, 3])) for i in tracked}
+    return tracked, {"voxel": voxel, "trunc": trunc, "origin": [float(x) for x in origin], "dims": [int(x) for x in dims],
+                     "iterations": rep["iterations"], "huber": rep["huber"], "frames": rep["frames"], "failed": rep["failed"],
+                     "observed_voxels": int((grid.weight > 0).sum()), "largest_correction": max(moved.values())}
+
+
+def _odometry(done, opts, H, W, inc, data_type, sensor2ego, dev, max_depth=80.0):
+    """Poses (and, with ``sweep_fraction``, twists) for the projected frames ``done``, in place; returns the report's ``"odometry"`` entry and its
+    ``"map_tracking"`` entry (None without ``map_tracking``)."""
     from . import registration, sweep
     fraction = opts.pop("sweep_fraction", None)
+    tracking = opts.pop("map_tracking", None)
     make = lambda fr: registration.frame_geometry(torch.from_numpy(np.ascontiguousarray(fr["depth"], np.float32)).to(dev),
                                                   torch.from_numpy(np.ascontiguousarray(fr["mask"])).to(dev), inc, int(H), int(W), data_type, sensor2ego)
     loop = opts.pop("loop_closure", None)
     if loop is not None and "sensor_height" not in loop:
         raise ValueError("ingest_point_clouds: loop_closure needs sensor_height (the height of the sensor above the ground, metres)")
+    if loop is not None and tracking is not None:
+        raise ValueError("ingest_point_clouds: map_tracking does not go with loop_closure")
     frames = {int(fr["id"]): make(fr) for fr in done} if loop is not None else _Geometries(done, make)     # the matcher describes all frames in one call
-    poses, rep = registration.odometry(frames, inclination=inc, data_type=data_type, sensor2ego=sensor2ego, **opts, **({"return_steps": True} if loop is not None else {}))
+    poses, rep = registration.odometry(frames, inclination=inc, data_type=data_type, sensor2ego=sensor2ego, **opts, **({"return_steps": True} if loop is not None or tracking is not None else {}))
     closed = None
     if loop is not None:
         from . import pose_graph
@@ -193,13 +239,16 @@ def _odometry(done, opts, H, W, inc, data_type, sensor2ego, dev) -> dict:
         closed = {**found, "cost": solved["cost"], "iterations": solved["iterations"], "converged": solved["converged"], "loops": solved["loops"],
                   "closure_error_chain": max((e["before"][0] for e in solved["loops"] if e["kind"] == "loop"), default=None),
                   "closure_error": max((e["after"][0] for e in solved["loops"] if e["kind"] == "loop"), default=None)}
+    tracked = None
+    if tracking is not None:
+        poses, tracked = _map_tracking(done, dict(tracking), frames, poses, rep["steps"], inc, data_type, sensor2ego, dev, max_depth)
     twists = sweep.twists_from_poses(poses, fraction) if fraction is not None else None
     for fr in done:
         fr["sensor2world"] = poses[int(fr["id"])]
         if twists is not None:
             fr["twist"] = twists[int(fr["id"])]
     return {"schedule": rep["schedule"], "pairs": rep["pairs"], "failed": rep["failed"], "first_pose": poses[min(poses)].tolist(),
-            **({"loop_closure": closed} if closed is not None else {})}
+            **({"loop_closure": closed} if closed is not None else {})}, tracked
 
 
 # ---- the command line ------------------------------------------------------------------------------------------------------------------------------------
@@ -297,9 +346,19 @@ def main(argv=None) -> int:
     ap.add_argument("--place-rings", type=int, default=None, help="--loop-closure: the rings of the descriptor (at most 32)")
     ap.add_argument("--place-sectors", type=int, default=None, help="--loop-closure: the sectors of the descriptor (at most 128 and --width)")
     ap.add_argument("--place-range", type=float, default=None, help="--loop-closure: the outer ground range of the descriptor [m]")
+    ap.add_argument("--map-tracking", action="store_true", help="--odometry: after the chain, fuse the frames into a TSDF grid sized from the chain's poses and "
+                    "align every frame to everything fused before it (lidar_rt_amd.map_registration); the tracked poses are written")
+    ap.add_argument("--map-voxel", type=float, default=0.2, help="--map-tracking: the voxel of the grid [m]")
+    ap.add_argument("--map-trunc", type=float, default=None, help="--map-tracking: the truncation distance [m] (default: 4 voxels)")
     ap.add_argument("--device", choices=("cpu", "cuda"), default=None)
     ap.add_argument("--batch", type=int, default=16)
     a = ap.parse_args(argv)
+    if a.map_tracking and not a.odometry:
+        print("ingest: --map-tracking goes with --odometry (it starts from the chain's steps)", file=sys.stderr)
+        return 2
+    if a.map_tracking and a.loop_closure:
+        print("ingest: --map-tracking does not go with --loop-closure: tracking against a map that a pose graph moves afterwards is not built yet", file=sys.stderr)
+        return 2
     if a.loop_closure and not a.odometry:
         print("ingest: --loop-closure goes with --odometry", file=sys.stderr)
         return 2
@@ -353,6 +412,7 @@ def main(argv=None) -> int:
                               notes={"pose_taken_from": borrowed, **({"sweep_fraction": float(a.sweep_fraction)} if a.sweep else {})}, twists=twists,
                               **({"odometry": {**({"first_pose": matrix_file(a.first_pose)} if a.first_pose else {}),
                                                **({"sweep_fraction": a.sweep_fraction} if a.sweep else {}),
+                                               **({"map_tracking": {"voxel": a.map_voxel, "trunc": a.map_trunc}} if a.map_tracking else {}),
                                                **({"loop_closure": {"sensor_height": a.sensor_height, "gap": a.loop_gap, "top": a.loop_top,
                                                                     **({"max_score": a.loop_max_score} if a.loop_max_score is not None else {}),
                                                                     **({"rings": a.place_rings} if a.place_rings is not None else {}),
@@ -367,6 +427,8 @@ def main(argv=None) -> int:
           f"{t['out_of_range']} out of range, {t['invalid']} invalid); " + (f"{len(rep['odometry']['failed'])} of {len(rep['odometry']['pairs'])} pairs kept the constant-velocity guess"
                                                                            if a.odometry else f"{len(borrowed)} frames took an earlier pose")
           + (f"; {len(rep['odometry']['loop_closure']['accepted'])} loops closed" if a.loop_closure else "")
+          + (f"; map tracking moved the chain by up to {rep['map_tracking']['largest_correction']:.3f} m, {len(rep['map_tracking']['failed'])} frames kept their start"
+             if a.map_tracking else "")
           + (f"; {rep['actors']['n_actors']} moving actors" if a.discover_actors else "") + f"; wrote {a.out}")
     return 0
 

@@ -271,8 +271,9 @@ def grid2sensor(origin, sensor2world):
     return np.ascontiguousarray(np.stack([np.linalg.inv(s) @ tr for s in S])[:, :3, :]) if len(S) else np.zeros((0, 3, 4))
 
 
-def _frames(grid, depth, mask, sensor2world, inclination, data_type, sensor2ego, intensity, min_depth, max_depth):
-    """The checked arguments of a call: (depth, mask uint8, intensity or None (F, H, W) on the grid's device, T (F, 3, 4), inc, off, yaw)."""
+def _frames(grid, depth, mask, sensor2world, inclination, data_type, sensor2ego, intensity, min_depth, max_depth, transforms=None):
+    """The checked arguments of a call: (depth, mask uint8, intensity or None (F, H, W) on the grid's device, T (F, 3, 4), inc, off, yaw).
+    ``transforms``: the (F, 3, 4) float64 grid2sensor to use as they are, instead of deriving them from ``sensor2world``."""
     if not isinstance(grid, TsdfGrid):
         raise MeshError("integrate: grid must be a TsdfGrid")
     dev = grid.device
@@ -293,7 +294,7 @@ def _frames(grid, depth, mask, sensor2world, inclination, data_type, sensor2ego,
         if not torch.is_tensor(intensity) or intensity.dtype != torch.float32 or intensity.numel() != F * H * W or intensity.device != dev:
             raise MeshError(f"integrate: intensity must be a float32 ({F}, {H}, {W}) tensor on {dev}")
         intensity = intensity.detach().reshape(F, H, W).contiguous()
-    T = grid2sensor(grid.origin, sensor2world)
+    T = grid2sensor(grid.origin, sensor2world) if transforms is None else np.ascontiguousarray(np.asarray(transforms, np.float64).reshape(-1, 3, 4))
     if T.shape[0] != F:
         raise MeshError(f"integrate: {T.shape[0]} poses for {F} frames")
     inc = ri._host_array("inclination", inclination, np.float64).reshape(-1)
@@ -320,13 +321,15 @@ def project_centres(cen, H, W, inclination, data_type, sensor2ego, T, min_depth,
 
 @torch.no_grad()
 def integrate_reference(grid, depth, mask, sensor2world, inclination, data_type="KITTI", sensor2ego=None, intensity=None, min_depth=0.0,
-                        max_depth=80.0):
+                        max_depth=80.0, transforms=None):
     """The numpy twin of ``integrate`` on a grid of CPU tensors, updated in place.  Returns ``margin``: the smallest distance of any voxel centre
-    that reached the projection's view test from a rounding boundary (``range_image.project_points_reference``), over the frames of the call."""
+    that reached the projection's view test from a rounding boundary (``range_image.project_points_reference``), over the frames of the call.
+    ``transforms``: the (F, 3, 4) float64 grid2sensor of the frames, used as they are (``sensor2world`` is not read then): what
+    ``map_registration.align_to_grid`` returns as ``G``."""
     if grid.device.type != "cpu":
         raise MeshError("integrate_reference: the twin works on a grid of CPU tensors")
     depth, mask, intensity, T, inc, off, yaw, min_depth, max_depth = _frames(grid, depth, mask, sensor2world, inclination, data_type, sensor2ego,
-                                                                             intensity, min_depth, max_depth)
+                                                                             intensity, min_depth, max_depth, transforms)
     F, H, W = depth.shape
     X, Y, Z = grid.dims
     cx, cy, cz = centres(grid.voxel, X), centres(grid.voxel, Y), centres(grid.voxel, Z)

@@ -36,7 +36,7 @@ setup(
     description="MI355X-native drop-in for the diff_lidar_tracer operator of LiDAR-RT (HIP, gfx950)",
     packages=find_packages(include=["lidar_rt_amd*", "diff_lidar_tracer*", "simple_knn*"]),
     py_modules=["chamfer_3D"],
-    package_data={"lidar_rt_amd": ["csrc/liblrt_hip.so", "csrc/liblrt_loss.so", "csrc/liblrt_gridcd.so", "csrc/liblrt_init.so", "csrc/liblrt_metrics.so", "csrc/liblrt_adam.so", "csrc/liblrt_densify.so", "csrc/liblrt_project.so", "csrc/liblrt_sweep.so", "csrc/liblrt_refine.so", "csrc/liblrt_sweepproj.so", "csrc/liblrt_unproject.so", "csrc/liblrt_actorsweep.so", "csrc/liblrt_beams.so", "csrc/liblrt_reg.so", "csrc/liblrt_segment.so", "csrc/liblrt_place.so", "csrc/liblrt_mesh.so", "csrc/liblrt_raycast.so", "csrc/liblrt_sweepfuse.so", "csrc/*.hip", "csrc/*.inc", "csrc/*.h", "csrc/*.cpp", "diff_lidar_tracer/_C_ext*.so"]},
+    package_data={"lidar_rt_amd": ["csrc/liblrt_hip.so", "csrc/liblrt_loss.so", "csrc/liblrt_gridcd.so", "csrc/liblrt_init.so", "csrc/liblrt_metrics.so", "csrc/liblrt_adam.so", "csrc/liblrt_densify.so", "csrc/liblrt_project.so", "csrc/liblrt_sweep.so", "csrc/liblrt_refine.so", "csrc/liblrt_sweepproj.so", "csrc/liblrt_unproject.so", "csrc/liblrt_actorsweep.so", "csrc/liblrt_beams.so", "csrc/liblrt_reg.so", "csrc/liblrt_segment.so", "csrc/liblrt_place.so", "csrc/liblrt_mesh.so", "csrc/liblrt_raycast.so", "csrc/liblrt_sweepfuse.so", "csrc/liblrt_mapreg.so", "csrc/*.hip", "csrc/*.inc", "csrc/*.h", "csrc/*.cpp", "diff_lidar_tracer/_C_ext*.so"]},
     python_requires=">=3.9",
     cmdclass={"build_py": BuildPy, "develop": Develop},
 )
